@@ -11,6 +11,12 @@ instead of SURVEY.md's 5 cm so that the barrier is active from the first Newton 
 Synthetic data only. Inputs are resident in HBM before the timed region.
 
   python bench.py --gpus N --steps K --warmup W         (N>1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds every other measurement of the line: the extra windows
+(`value_windows`), the pinned placement, the HBM-resident SpMV pass and secondary workload, the drop-in leg, the CPU baseline, the SpMV's
+back-to-back launches (`roofline.live.back_to_back`) and, for N > 1, the RCCL leg and the solo kernels of the fused PCG iteration.
+`--dump-outputs DIR` writes the state the timed path ends in (positions and velocities of the block's points, the box's rigid-body state) as
+DIR/<name>.npy in float64.
 """
 import argparse
 import json
@@ -72,6 +78,30 @@ def run_newton_steps(sim, S, capi, n_steps):
             continue
     i = sim.info()
     return i.total_newton_iterations - n0, i.total_linear_solves - ls0, i.total_cg_iterations - cg0, i.total_linear_solve_time - tl0
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(sim, out_dir, scene):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as out_dir/<name>.npy (float64): x.npy / v.npy = positions /
+    velocities of the block's points (n x 3), box_state.npy = the rigid box's translation, quaternion, velocity, angular velocity (13 values).
+    A grid whose arrays exceed DUMP_LIMIT_BYTES writes the same seeded sample of rows of x and v, and the row numbers as sample_rows.npy."""
+    import numpy as np
+
+    arrays = {"x": sim.points("x0"), "v": sim.points("v0")}
+    if scene == "contact":
+        arrays["box_state"] = np.concatenate(sim.rb_state(0))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = arrays["x"].shape[0]
+        keep = (DUMP_LIMIT_BYTES - (1 << 12)) // (arrays["x"].itemsize * 6 + 8)   # x and v rows + the row number, headers' room aside
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays["x"], arrays["v"] = arrays["x"][rows], arrays["v"][rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def host_cpu():
@@ -507,8 +537,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--grid", type=str, default="44,44,43", help="hexahedra per dimension (12 tets each)")
     ap.add_argument("--scene", type=str, default="contact", choices=["contact", "clamped"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements of the default workload (pinned placement, HBM-resident SpMV pass)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline figure (extra windows, pinned placement, "
+                                                         "HBM-resident pass, drop-in, CPU baseline, back-to-back SpMV launches, N > 1: RCCL leg, solo kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the timed steps end in as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements of the default workload (pinned placement, HBM-resident SpMV pass)")
     ap.add_argument("--offset", type=str, default="0,0", help="block moved off the box's axes by (ox, oy) metres: the placement on which the reference reproduces itself "
                                                               "and the engine's Newton / solve / CG counts equal its log (DESIGN.md section 5); default: centred")
     a = ap.parse_args()
@@ -530,7 +563,7 @@ def main():
     # N > 1 on the default workload also runs the same scene at HBM_GRID (7.99 M tets: each of 8 ranks then holds what one GPU holds at
     # configs[3], the regime the row-sharded design is for) and reports it as config.secondary; N = 1 reports the same run beside the
     # HBM-resident SpMV figure, so that a reader has the one-GPU number the N-GPU one divides by
-    secondary_wanted = a.scene == "contact" and (nx, ny, nz) == (44, 44, 43) and offset == (0.0, 0.0) and not a.no_extras
+    secondary_wanted = a.scene == "contact" and (nx, ny, nz) == (44, 44, 43) and offset == (0.0, 0.0) and a.full and not a.no_extras
     dist = None
     uid = None
     comm = None
@@ -710,6 +743,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(sim, a.dump_outputs, a.scene)
     import ctypes as _C0
     _ov = _C0.c_double()
     spmv_ev_overhead_ms = _ov.value if capi.lib().mistark_spmv_event_overhead(sim.engine_handle(), _C0.byref(_ov)) == 0 and _ov.value > 0 else None
@@ -723,7 +758,7 @@ def main():
     # N > 1 over windows: solo durations of the fused PCG iteration's two kernels on every rank's rows (the ranks take turns: valid on a box
     # where all ranks share one GPU, too)
     fused_kernels_us = None
-    if world > 1 and comm is not None:
+    if world > 1 and comm is not None and a.full:
         import ctypes as _C1
         mine = None
         capi.lib().mistark_set_option(sim.engine_handle(), b"spmv_grid_cap", 0)  # (a rank measuring alone needs no cap: the grid a GPU of its own would get)
@@ -741,7 +776,7 @@ def main():
         else:
             fused_kernels_us = {"unavailable": [v for v in every if not isinstance(v, list)][0]}
     spmv_b2b_ms = None
-    if rank == 0:
+    if rank == 0 and a.full:
         import ctypes as _C
         us = _C.c_double()
         if capi.lib().mistark_spmv_bench(sim.engine_handle(), 100, _C.byref(us)) == 0:
@@ -790,7 +825,10 @@ def main():
         # beside the model DESIGN.md ("Multi-GPU") derives the expected scaling from
         per_rank = allgather_bytes({k: 1e3 * v / max(newton, 1) for k, v in stage.items()})
         stages_table = stage_table(per_rank, world, newton, n_ls, n_cg, ranks_seen, 1e3 * elapsed / max(newton, 1))
-        rccl_leg, rccl_hung = rccl_allreduce_leg(capi, dist, rank, world, device, ranks_seen, broadcast_uid, allgather_bytes, info.ndofs)
+        if a.full:
+            rccl_leg, rccl_hung = rccl_allreduce_leg(capi, dist, rank, world, device, ranks_seen, broadcast_uid, allgather_bytes, info.ndofs)
+        else:
+            rccl_leg = {"ranks": None, "skipped": "not measured without --full", "allreduce_ndofs_us": None, "allreduce_3_us": None}
     if rank == 0:
         traffic, traffic_src = profile_traffic()
         trace_ms, trace_src = profile_kernel_trace()
@@ -907,14 +945,14 @@ def main():
             },
         }
         out["value_windows"] = None
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             sim.close()
             sim = None
             try:
                 out["value_windows"] = extra_windows(S, capi, nx, ny, nz, device, a.scene, offset, a.steps, a.warmup, out)
             except Exception as e:  # noqa: BLE001
                 out["value_windows"] = {"unavailable": repr(e)}
-        if default_workload and offset == (0.0, 0.0) and not a.no_extras:
+        if default_workload and offset == (0.0, 0.0) and a.full and not a.no_extras:
             if sim is not None:
                 sim.close()
             sim = None
@@ -932,10 +970,10 @@ def main():
                 out["pinned_placement"] = pinned_placement_run(S, capi, nx, ny, nz, device, a.steps, a.warmup, not a.no_cpu_baseline)
             except Exception as e:  # noqa: BLE001
                 out["pinned_placement"] = {"unavailable": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nx, ny, nz, a.scene, offset)
         else:
-            out["cpu_baseline"] = {"value": None, "unit": "Newton-steps/s", "cores": 0, "kind": "reference", "sample": "skipped (N>1 or --no-cpu-baseline)"}
+            out["cpu_baseline"] = {"value": None, "unit": "Newton-steps/s", "cores": 0, "kind": "reference", "sample": "skipped (N>1, no --full or --no-cpu-baseline)"}
         print(json.dumps(out))
     if rccl_hung:
         # a thread of this process still sits in ncclCommInitRank / an all-reduce that never completed: the line is out, leave without the

@@ -108,3 +108,58 @@ def test_one_gpu_line_has_a_measured_stage_column_and_value_windows(monkeypatch)
     assert all(k in w for k in b.VALUE_WINDOWS_KEYS)
     assert w["windows"] == 1 + b.EXTRA_WINDOWS == len(w["values"]) and w["values"][0] == 160.0 and w["min"] <= w["median"] <= w["max"]
     assert calls == ["close"] * b.EXTRA_WINDOWS
+
+
+def test_help_lists_full_and_dump_outputs():
+    r = _run(["--help"])
+    assert r.returncode == 0 and b"--full" in r.stdout and b"--dump-outputs" in r.stdout
+
+
+def test_plain_run_leaves_every_other_measurement_to_full():
+    """A plain run times the K steps and prints the line; the legs beside the headline figure only run with --full (source check: the line
+    itself needs a GPU)."""
+    lines = open(os.path.join(ROOT, "bench.py")).read().split("\n")
+    start = lines.index("def main():")
+    for call in ("extra_windows(", "hbm_resident_pass(", "drop_in_run(", "pinned_placement_run(", "cpu_baseline(nx", "mistark_spmv_bench(sim.engine_handle(), 100",
+                 "mistark_dist_fused_bench(", "rccl_allreduce_leg(capi"):
+        i = next(j for j in range(start, len(lines)) if call in lines[j])
+        indent, guards = len(lines[i]) - len(lines[i].lstrip()), []
+        for line in reversed(lines[start:i]):   # the headers of the blocks the call sits in
+            d = len(line) - len(line.lstrip())
+            if line.strip() and d < indent:
+                guards.append(line.strip())
+                indent = d
+        assert any(g.startswith("if ") and "a.full" in g for g in guards), (call, guards)
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    b = _bench()
+
+    class Sim:
+        def __init__(self, n):
+            self.n = n
+
+        def points(self, which):
+            return np.random.default_rng({"x0": 1, "v0": 2}[which]).standard_normal((self.n, 3))
+
+        def rb_state(self, rb):
+            assert rb == 0
+            return np.arange(3.0), np.array([1.0, 0, 0, 0]), np.zeros(3), np.zeros(3)
+
+    sim = Sim(1000)
+    b.dump_outputs(sim, str(tmp_path / "small"), "contact")
+    x, v, box = (np.load(tmp_path / "small" / (k + ".npy")) for k in ("x", "v", "box_state"))
+    assert x.dtype == v.dtype == box.dtype == np.float64 and x.shape == v.shape == (1000, 3) and box.shape == (13,)
+    assert (x == sim.points("x0")).all() and not (tmp_path / "small" / "sample_rows.npy").exists()
+
+    # over the limit: the same seeded sample of rows, the same in every run
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 30_000)
+    for d in ("a", "b"):
+        b.dump_outputs(sim, str(tmp_path / d), "clamped")
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert total <= 30_000 and not (tmp_path / "a" / "box_state.npy").exists()
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert (rows == np.load(tmp_path / "b" / "sample_rows.npy")).all() and 0 < len(rows) < 1000
+    assert (np.load(tmp_path / "a" / "x.npy") == sim.points("x0")[rows.astype(np.int64)]).all()

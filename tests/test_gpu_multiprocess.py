@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRID = "12,12,12"
-ARGS = ["--steps", "8", "--warmup", "2", "--grid", GRID, "--no-cpu-baseline"]
+ARGS = ["--steps", "8", "--warmup", "2", "--grid", GRID, "--no-cpu-baseline", "--full"]   # (--full: the N > 1 lines carry the RCCL leg)
 
 
 def _free_port():

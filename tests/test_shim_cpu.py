@@ -1,4 +1,5 @@
-"""CPU (build container only: needs oracle/_ref/shim_check, which `make -C oracle shim` builds from /root/reference): the B-upper
+"""CPU (oracle/_ref/shim_check, which `make -C oracle shim` builds from the reference's sources, where it was built; elsewhere the
+descriptions it wrote, stored under tests/golden/shim/): the B-upper
 boundary of SURVEY.md 8(b). The UNMODIFIED reference (stark/src/** compiled in place against shim/include/symx, i.e. with
 symx::NewtonsMethod replaced by the shim over the C ABI) builds a scene through its own stark::Simulation; its first time step makes
 the shim register every DoF set, array and potential with a registration-only libmistark context (no GPU). What arrives at the C ABI
@@ -17,8 +18,26 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SHIM_CHECK = os.path.join(ROOT, "oracle", "_ref", "shim_check")
+GOLDEN_SHIM = os.path.join(ROOT, "tests", "golden", "shim")
 
-pytestmark = pytest.mark.skipif(not os.path.exists(SHIM_CHECK), reason="oracle/_ref/shim_check not built (needs /root/reference: make -C oracle shim)")
+
+def _reference_description(binary, scene, tmp_path):
+    """What the unmodified reference registers through the shim for `scene` (MISTARK_SHIM_DESCRIBE of a registration-only run of
+    oracle/_ref/<binary>). Where the binary was built it runs, and what it writes must equal the stored copy
+    tests/golden/shim/<binary>_<scene>.json; elsewhere the stored copy stands in for it."""
+    with open(os.path.join(GOLDEN_SHIM, "%s_%s.json" % (binary, scene))) as f:
+        stored = json.load(f)
+    exe = os.path.join(ROOT, "oracle", "_ref", binary)
+    if not os.path.exists(exe):
+        return stored
+    out = str(tmp_path / (binary + ".json"))
+    env = dict(os.environ, MISTARK_SHIM_DRY="1", MISTARK_SHIM_DESCRIBE=out, SHIM_SCRATCH=str(tmp_path))
+    r = subprocess.run([exe, scene], env=env, capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    with open(out) as f:
+        live = json.load(f)
+    assert live == stored, "%s %s: the registration differs from tests/golden/shim/%s_%s.json" % (binary, scene, binary, scene)
+    return live
 
 
 def _describe(h):
@@ -84,11 +103,7 @@ def _normalise(d):
 
 @pytest.mark.parametrize("scene", ["blockbox", "mixed", "tetbeam", "cloth"])
 def test_reference_classes_register_what_the_mirror_registers(scene, tmp_path):
-    out = str(tmp_path / "shim.json")
-    env = dict(os.environ, MISTARK_SHIM_DRY="1", MISTARK_SHIM_DESCRIBE=out, SHIM_SCRATCH=str(tmp_path))
-    r = subprocess.run([SHIM_CHECK, scene], env=env, capture_output=True, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    ref = json.load(open(out))
+    ref = _reference_description("shim_check", scene, tmp_path)
     ours = _mirror(scene)
     # DoF sets: same labels, sizes and order (Simulation.cpp:88-89: soft.v1 | rigid.v1 | rigid.w1)
     assert ref["dof_sets"] == ours["dof_sets"]
@@ -132,16 +147,7 @@ def test_the_collision_detection_stand_in_changes_nothing_that_is_registered(sce
     detector dependency replaced by include/mistark_tmcd.h) instead of the dependency's own header. In registration-only mode (no GPU: the
     stand-in returns empty lists) EnergyFrictionalContact registers the same DoF sets and the same potentials with the same bindings as with
     its own detector; only the number of rows its host detection had already found differs."""
-    exe = SHIM_CHECK + "_cd"
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/shim_check_cd not built (make -C oracle shim_cd)")
-    got = []
-    for binary in (SHIM_CHECK, exe):
-        out = str(tmp_path / (os.path.basename(binary) + ".json"))
-        env = dict(os.environ, MISTARK_SHIM_DRY="1", MISTARK_SHIM_DESCRIBE=out, SHIM_SCRATCH=str(tmp_path))
-        r = subprocess.run([binary, scene], env=env, capture_output=True, timeout=300)
-        assert r.returncode == 0, r.stderr.decode()[-2000:]
-        got.append(json.load(open(out)))
+    got = [_reference_description(binary, scene, tmp_path) for binary in ("shim_check", "shim_check_cd")]
     assert got[0]["dof_sets"] == got[1]["dof_sets"]
     A, B = _normalise(got[0]), _normalise(got[1])
     assert set(A) == set(B) and len(A) >= 35
@@ -158,11 +164,7 @@ def test_user_defined_potential_takes_the_sequence_branch_of_the_shim(scene, nam
     """A name the engine has no kernel for (README.md:109-126 of the reference): the shim flattens the expression into SymX's op sequence and
     registers it with mistark_potential_custom; `foreach` carries a summation loop (MappedWorkspace::add_for_each), whose symbols get a binding
     of their own (a global slot of 4 doubles: the pole) at the place the summation vector was made."""
-    out = str(tmp_path / "shim.json")
-    env = dict(os.environ, MISTARK_SHIM_DRY="1", MISTARK_SHIM_DESCRIBE=out, SHIM_SCRATCH=str(tmp_path))
-    r = subprocess.run([SHIM_CHECK, scene], env=env, capture_output=True, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    d = json.load(open(out))
+    d = _reference_description("shim_check", scene, tmp_path)
     p = [q for q in d["potentials"] if q["name"] == name]
     assert len(p) == 1 and p[0]["n_elem"] == 4 ** 3 + 3 ** 3 and p[0]["conn_stride"] == 1
     bs = p[0]["bindings"]
