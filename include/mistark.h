@@ -306,8 +306,6 @@ int mistark_newton_solve(mistark_ctx* ctx, const mistark_newton_settings* settin
  * "contact_closed_min_lanes" = N: closed-form contact kernels for tables with at least N (contact, DoF pair) lanes, 0 = always, default
  * -1 = by potential, see launch_eval);
  * "generic_inertia" = EnergyLumpedInertia through the generic kernel (six lanes per node; default: one lane per node, the same bits);
- * "pin_host_arrays" = page-lock the caller's large DoF and bound arrays where they are (hipHostRegister, checked; released when an array is
- * rebound or resized and with the context; a range that cannot be locked stays pageable) so that transfers to and from them are direct DMA;
  * "atomic_assembly" = scatter assembly with float atomics
  * instead of the deterministic gather; "proj_variant" = PSD projection cross-checks, bits: 1 = eigen-decomposition with the
  * matrix in LDS instead of registers, 2 = one launch per potential instead of one for all short lists, 4 = IEEE division /
@@ -320,8 +318,7 @@ int mistark_newton_solve(mistark_ctx* ctx, const mistark_newton_settings* settin
  * "no_multi_eval_p" = one launch per potential in energy-only evaluations (default: the small potentials share one launch);
  * "no_eval_prelaunch" = do not start the large potentials' kernels ahead of the callback that precedes an evaluation;
  * "no_pattern_overlap" / "no_eval_overlap" / "no_bounded_pattern" = switch off, one by one, the side stream for the contact part's
- * pattern, the auxiliary stream for small potentials, the device-side counts of the pattern build; "fuse_dir" = direction update
- * inside the SpMV (measured slower, a cross-check); "kernel_dbg" = measurement switches inside kernels.
+ * pattern, the auxiliary stream for small potentials, the device-side counts of the pattern build.
  * Returns 0, or < 0 for an unknown name. The environment variable
  * MISTARK_OPTIONS="name=value,name=value" applies the same switches inside mistark_create (for a process that cannot be
  * edited: a test suite, a profiler run); a bad entry makes mistark_create fail with -6. MISTARK_POISON=1 fills every fresh
@@ -346,8 +343,7 @@ int mistark_spmv_bench(mistark_ctx* ctx, int n_launches, double* avg_us);
 /* Waits until everything queued on the engine's stream has finished (entry points that return values already do; assemble / project /
  * axpby only enqueue). For timing from the host. */
 int mistark_sync(mistark_ctx* ctx);
-/* Event counters of the context, by name (tests assert that a feature under test actually ran): "proj_speculated" / "proj_adopted" (projection
- * rounds started beside a solve / taken over by the retry, option proj_speculation), "dof_skips_verified" (MISTARK_VERIFY_DOF_SKIP=1: DoF
+/* Event counters of the context, by name (tests assert that a feature under test actually ran): "dof_skips_verified" (MISTARK_VERIFY_DOF_SKIP=1: DoF
  * transfers skipped at an unchanged iterate and checked against a real transfer), "fused_solves" / "unfused_solves" (sharded PCG),
  * "rtc_builds" / "rtc_launches" / "rtc_build_ms" (user-defined potentials: kernels emitted and compiled by hipRTC, their launches, build time),
  * "multi_pgh_launches" (evaluations whose contact / friction tables shared one launch; option no_multi_eval_pgh = 1: one launch per table),

@@ -258,7 +258,6 @@ int mistark_resize_dof_set(mistark_ctx* ctx, int set, double* host, int64_t n_sc
     if (n_scalars > 0 && !host) throw Error("DoF set without a host array");
     Context& c = ctx->c;
     const double* old = c.dof_sets[set].host;
-    if (old != host || c.dof_sets[set].n != n_scalars) host_range_unpin(c, old);
     c.dof_sets[set].host = host;
     c.dof_sets[set].n = n_scalars;
     for (auto& a : c.arrays)
@@ -330,11 +329,6 @@ int mistark_array_rebind(mistark_ctx* ctx, int array, const double* host, int64_
     if (array < 0 || array >= (int)c.arrays.size()) throw Error("bad array id");
     Array& a = c.arrays[array];
     if (a.dof_set >= 0) throw Error("use mistark_resize_dof_set for DoF arrays");
-    if (a.host != host || a.n_items != n_items) {
-        bool shared = false;  // (another array — the same container bound at another stride — may still be on the old range)
-        for (const Array& o : c.arrays) shared = shared || (&o != &a && o.host == a.host);
-        if (!shared) host_range_unpin(c, a.host);
-    }
     a.host = host;
     a.n_items = n_items;
     a.need_upload = true;
@@ -554,12 +548,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     Context& c = ctx->c;
     if (!name || !out) throw Error("mistark_get_counter: null argument");
     const std::string n = name;
-    if (n == "proj_speculated") *out = c.n_proj_speculated;
-    else if (n == "proj_adopted") *out = c.n_proj_adopted;
-    else if (n == "multi_pgh_launches") *out = c.n_multi_pgh;
+    if (n == "multi_pgh_launches") *out = c.n_multi_pgh;
     else if (n == "dof_skips_verified") *out = c.n_dof_skips_verified;
-    else if (n == "host_ranges_pinned") *out = c.n_pin_ok;
-    else if (n == "host_ranges_not_pinned") *out = c.n_pin_failed;
     else if (n == "rtc_builds") *out = c.n_rtc_builds;
     else if (n == "custom_kernel_us") *out = (int64_t)c.custom_kernel_us;
     else if (n == "rtc_launches") *out = c.n_rtc_launches;
@@ -585,10 +575,7 @@ int mistark_dofs_to_host_arrays(mistark_ctx* ctx)
     Context& c = ctx->c;
     prepare(c);
     for (auto& s : c.dof_sets)
-        if (s.n > 0) {
-            (void)host_range_pinned(c, s.host, (size_t)s.n * sizeof(double));
-            MS_CHECK(hipMemcpyAsync(s.host, c.u.p + s.offset, s.n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        }
+        if (s.n > 0) MS_CHECK(hipMemcpyAsync(s.host, c.u.p + s.offset, s.n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     MS_CHECK(hipStreamSynchronize(c.stream));
     c.u_host_version = c.u_version;
     API_END(0)
@@ -600,10 +587,7 @@ int mistark_dofs_to_host_arrays_if_changed(mistark_ctx* ctx)
     prepare(c);
     if (c.u_host_version != c.u_version) {
         for (auto& s : c.dof_sets)
-            if (s.n > 0) {
-                (void)host_range_pinned(c, s.host, (size_t)s.n * sizeof(double));
-                MS_CHECK(hipMemcpyAsync(s.host, c.u.p + s.offset, s.n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-            }
+            if (s.n > 0) MS_CHECK(hipMemcpyAsync(s.host, c.u.p + s.offset, s.n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
         MS_CHECK(hipStreamSynchronize(c.stream));
         c.u_host_version = c.u_version;
     } else {
@@ -635,10 +619,7 @@ int mistark_dofs_from_host_arrays(mistark_ctx* ctx)
     Context& c = ctx->c;
     prepare(c);
     for (auto& s : c.dof_sets)
-        if (s.n > 0) {
-            (void)host_range_pinned(c, s.host, (size_t)s.n * sizeof(double));
-            MS_CHECK(hipMemcpyAsync(c.u.p + s.offset, s.host, s.n * sizeof(double), hipMemcpyHostToDevice, c.stream));
-        }
+        if (s.n > 0) MS_CHECK(hipMemcpyAsync(c.u.p + s.offset, s.host, s.n * sizeof(double), hipMemcpyHostToDevice, c.stream));
     MS_CHECK(hipStreamSynchronize(c.stream));
     API_END(0)
 }
@@ -1251,45 +1232,30 @@ int mistark_set_option(mistark_ctx* ctx, const char* name, int value)
     else if (n == "no_eval_prelaunch") ctx->c.no_eval_prelaunch = value != 0;
     else if (n == "no_multi_eval_p") ctx->c.no_multi_eval_p = value != 0;
     else if (n == "no_multi_eval_pgh") ctx->c.no_multi_eval_pgh = value != 0;
-    else if (n == "late_eager_assembly") ctx->c.late_eager_assembly = value != 0;
     else if (n == "llt_multifrontal") ctx->c.llt_multifrontal = value;
     else if (n == "llt_no_coords") { ctx->c.llt_no_coords = value != 0; ctx->c.llt_mf_pattern_version = 0; }
-    else if (n == "pcg_holdback") ctx->c.pcg_holdback = value != 0;
-    else if (n == "sweep_axis_by_extent") ctx->c.sweep_axis_by_extent = value != 0;
-    else if (n == "pin_host_arrays") ctx->c.pin_host_arrays = value != 0;
     else if (n == "generic_inertia") ctx->c.generic_inertia = value != 0;
     else if (n == "contact_closed_min_lanes") ctx->c.contact_closed_min_lanes = value;
     else if (n == "atomic_assembly") ctx->c.atomic_assembly = value != 0;
     else if (n == "spmv_grid_cap") ctx->c.spmv_grid_cap = value;
     else if (n == "spmv_nt") ctx->c.spmv_nt = value;
     else if (n == "custom_rtc") ctx->c.custom_rtc = value;
-    else if (n == "hf_layout") {  // (the pool is rewritten by the next evaluation; the gather's descriptors follow the layout)
-        ctx->c.hf_layout = value;
-        ctx->c.part[0].desc_lazy = ctx->c.part[1].desc_lazy = -1;
-        ctx->c.matrix_current = false;
-        ctx->c.static_assembled = false;
-    }
     else if (n == "custom_timing") ctx->c.custom_timing = value;
     else if (n == "pcg_batch") ctx->c.pcg_batch = value;
     else if (n == "lazy_hessians") ctx->c.lazy_allowed = value != 0;  // newton_solve: float upper-triangle pool for the closed-form tets
-    else if (n == "kernel_dbg") { ctx->c.kernel_dbg = value; ctx->c.layout_dirty = true; }  // measurement only
     else if (n == "lazy_eval") ctx->c.lazy_eval = value != 0;
     else if (n == "no_pattern_overlap") ctx->c.no_pattern_overlap = value != 0;
     else if (n == "no_eval_overlap") ctx->c.no_eval_overlap = value != 0;
-    else if (n == "contact_speculation") ctx->c.contact_speculation = value != 0;
     else if (n == "no_eager_assembly") ctx->c.no_eager_assembly = value != 0;
     else if (n == "no_sym_gather") ctx->c.no_sym_gather = value != 0;
     else if (n == "no_split_gather") ctx->c.no_split_gather = value != 0;
     else if (n == "no_bounded_pattern") { ctx->c.no_bounded_pattern = value != 0; ctx->c.part[1].dirty = true; }
-    else if (n == "fuse_dir") ctx->c.no_fuse_dir = value == 0;
     else if (n == "no_grad_gather") { ctx->c.no_grad_gather = value != 0; ctx->c.layout_dirty = true; }         // staged mistark_eval calls take the lazy path too (tests)
 
     else if (n == "spmv_variant") ctx->c.spmv_variant = value;
     else if (n == "proj_variant") ctx->c.proj_variant = value;
     else if (n == "no_contact_cache") ctx->c.no_contact_cache = value != 0;
     else if (n == "no_sharded_search") ctx->c.no_sharded_search = value != 0;
-    else if (n == "seg_sort") ctx->c.seg_sort = value != 0;
-    else if (n == "proj_speculation") ctx->c.proj_speculation = value != 0;
     else if (n == "no_row_order") { ctx->c.no_row_order = value != 0; ctx->c.perm_sig.clear(); ctx->c.layout_dirty = true; }  // one GPU: the caller's row numbering in the solver, too
     else if (n == "row_order") { ctx->c.row_order_mode = value; ctx->c.perm_sig.clear(); ctx->c.layout_dirty = true; }
     else if (n == "atomic_projection") ctx->c.atomic_projection = value != 0;

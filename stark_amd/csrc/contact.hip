@@ -538,138 +538,6 @@ __global__ __launch_bounds__(CB) void k_bp_gather(ContactDev d, Bands B, const u
     for (int k = 0; k < 6; k++) s_aabb[6 * (size_t)j + k] = b[k];
     s_lo[j] = b[B.axis];
 }
-// ---- the sorted box list without a general sort (round 4) ---------------------------------------------------------------------------------
-// The list is 3 * NBANDS segments (class, band), each sorted by the lower bound along the sweep axis. The radix sort of 41-bit keys that used to
-// produce it was ten launches of the sorting library plus two scans and two fills around it — the longest piece of a search's launch chain (a
-// search is ~35 dependent launches of ~5 us whatever their size). Three launches do the same: k_bp_hist counts the entries of every segment
-// (LDS histograms, one global atomic per workgroup and touched segment), k_bp_scatter drops every entry {order-preserving lower bound, primitive}
-// into its segment (positions from LDS ranks inside a range the workgroup reserved: any order), k_seg_sort sorts each segment in LDS by one
-// workgroup quartet (rank sort; the primitive index breaks ties, which is the order the stable radix sort left) and writes the sweep's inputs (sorted
-// boxes, lower bounds, index words, segment starts) itself. A segment beyond SEG_SORT_MAX entries raises counters[58]: the host falls back to
-// the library sort for good.
-// MEASURED (configs[3], 69 k boxes, segments of 700-2100 entries; option "seg_sort"): not a win, OFF by default. The rank sort reads n keys out
-// of LDS per entry — a broadcast read still occupies the LDS pipeline for a whole wavefront — 227 us; a bitonic network in LDS with 1024 threads
-// 78 us (55-105 barrier-separated steps); the library's radix sort chain ~70 us of kernels. And the search's wait did not move when the sort took
-// 78 instead of 70 us in a third of the launches (5.1 against 4.9 ms over 38 searches): the chain is bound by the sweeps (63-89 us + 10-20 us
-// each) and the read-back, not by launch count. Kept as a cross-check of the sorted list (identical tables, tests/test_gpu_contact.py).
-constexpr int N_SEG = 3 * NBANDS;
-constexpr int SEG_SORT_MAX = 8192;
-constexpr int SEG_SORT_THREADS = 1024;
-__device__ __forceinline__ int seg_of_box(const ContactDev& d, int i) { return i < d.n_v ? 0 : (i < d.n_v + d.n_t ? 1 : 2); }
-__global__ __launch_bounds__(CB) void k_bp_hist(ContactDev d, Bands B, uint32_t* __restrict__ hist)
-{
-    __shared__ uint32_t sh[N_SEG];
-    for (int t = threadIdx.x; t < N_SEG; t += CB) sh[t] = 0u;
-    __syncthreads();
-    const int i = blockIdx.x * CB + threadIdx.x;
-    const int n = d.n_v + d.n_t + d.n_e;
-    if (i < n) {
-        const float* b = d.aabb + 6 * (size_t)i;
-        const int b0 = band_of(B, b[B.band_axis]), b1 = band_of(B, b[3 + B.band_axis]), cls = seg_of_box(d, i);
-        for (int k = b0; k <= b1; k++) atomicAdd(&sh[cls * NBANDS + k], 1u);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < N_SEG; t += CB)
-        if (sh[t]) atomicAdd(&hist[t], sh[t]);
-}
-// hist -> segment starts (every workgroup scans the 192 counts itself); cursor[seg] = entries handed out so far
-__global__ __launch_bounds__(CB) void k_bp_scatter(ContactDev d, Bands B, const uint32_t* __restrict__ hist, uint32_t* __restrict__ cursor, uint64_t* __restrict__ ekeys, int cap,
-                                                  int* __restrict__ counters)
-{
-    __shared__ uint32_t start[N_SEG + 1], cnt[N_SEG], rank[N_SEG], base[N_SEG];
-    // (every thread fetches one count, then sums the counts before its own out of LDS: a single thread walking the 192 counts in global memory
-    // was a chain of dependent loads at the head of every workgroup)
-    for (int t = threadIdx.x; t < N_SEG; t += CB) {
-        base[t] = hist[t];
-        cnt[t] = rank[t] = 0u;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t <= N_SEG; t += CB) {
-        uint32_t at = 0;
-        for (int u = 0; u < t; u++) at += base[u];
-        start[t] = at;
-        if (t == N_SEG && blockIdx.x == 0) counters[3] = (int)at;  // number of entries (the host checks it against the capacity)
-    }
-    __syncthreads();
-    const int i = blockIdx.x * CB + threadIdx.x;
-    const int n = d.n_v + d.n_t + d.n_e;
-    int b0 = 0, b1 = -1, cls = 0;
-    uint32_t fk = 0u;
-    if (i < n) {
-        const float* b = d.aabb + 6 * (size_t)i;
-        b0 = band_of(B, b[B.band_axis]);
-        b1 = band_of(B, b[3 + B.band_axis]);
-        cls = seg_of_box(d, i);
-        fk = float_key(b[B.axis]);
-    }
-    // the workgroup's entries per segment (LDS atomics), one global reservation per touched segment, then the stores at LDS ranks inside it
-    for (int k = b0; k <= b1; k++) atomicAdd(&cnt[cls * NBANDS + k], 1u);
-    __syncthreads();
-    for (int t = threadIdx.x; t < N_SEG; t += CB) base[t] = cnt[t] ? atomicAdd(&cursor[t], cnt[t]) : 0u;
-    __syncthreads();
-    for (int k = b0; k <= b1; k++) {
-        const int sg = cls * NBANDS + k;
-        const uint32_t pos = start[sg] + base[sg] + atomicAdd(&rank[sg], 1u);
-        if (pos < (uint32_t)cap) ekeys[pos] = ((uint64_t)fk << 32) | (uint64_t)(uint32_t)i;
-    }
-}
-constexpr int SEG_PARTS = 4;  // workgroups per segment: each ranks a quarter of the segment's entries against all of them
-__global__ __launch_bounds__(SEG_SORT_THREADS) void k_seg_sort(ContactDev d, Bands B, const uint32_t* __restrict__ hist, const uint64_t* __restrict__ ekeys, int cap,
-                                                             uint32_t* __restrict__ sidx, float* __restrict__ s_aabb, float* __restrict__ s_lo, int* __restrict__ seg,
-                                                             int* __restrict__ counters)
-{
-    __shared__ uint64_t sh[SEG_SORT_MAX];
-    __shared__ uint32_t hs[N_SEG];
-    __shared__ uint32_t s_start, s_n, s_total;
-    const int sg = blockIdx.x / SEG_PARTS, part = blockIdx.x % SEG_PARTS;
-    for (int t = threadIdx.x; t < N_SEG; t += SEG_SORT_THREADS) hs[t] = hist[t];
-    __syncthreads();
-    if (threadIdx.x < 64) {  // one wavefront adds the counts before this segment and all of them
-        uint32_t before = 0, all = 0;
-        for (int t = threadIdx.x; t < N_SEG; t += 64) {
-            all += hs[t];
-            if (t < sg) before += hs[t];
-        }
-        for (int dd = 32; dd >= 1; dd >>= 1) {
-            before += __shfl_down(before, dd, 64);
-            all += __shfl_down(all, dd, 64);
-        }
-        if (threadIdx.x == 0) {
-            s_start = before;
-            s_n = hs[sg];
-            s_total = all;
-            if (part == 0) seg[sg] = (int)before;
-            if (blockIdx.x == 0) seg[N_SEG] = all > (uint32_t)cap ? 0 : (int)all;  // (a list that did not fit is not swept: the host grows it and searches again)
-        }
-    }
-    __syncthreads();
-    const uint32_t start = s_start, n = s_n;
-    if (s_total > (uint32_t)cap) return;  // (the list did not fit: the host grows it and searches again)
-    if (n > (uint32_t)SEG_SORT_MAX) {
-        if (threadIdx.x == 0) counters[58 - 48] = 1;  // (counters = the search's counters + 48)
-        return;
-    }
-    if (n == 0) return;
-    // Rank sort: the whole segment in LDS, every thread counts the keys below its own (all lanes read the same LDS word: a broadcast, no
-    // barrier behind the load). The keys are distinct (the primitive breaks ties), so the rank is the sorted position — the order the stable
-    // radix sort left. A few hundred to a few thousand entries per segment: n^2 / 4096 LDS reads per thread.
-    for (uint32_t t = threadIdx.x; t < n; t += SEG_SORT_THREADS) sh[t] = ekeys[start + t];
-    __syncthreads();
-    const uint32_t band = (uint32_t)(sg % NBANDS);
-    const uint32_t per = (n + SEG_PARTS - 1) / SEG_PARTS, t_begin = (uint32_t)part * per, t_end = min(n, t_begin + per);
-    for (uint32_t t = t_begin + threadIdx.x; t < t_end; t += SEG_SORT_THREADS) {
-        const uint64_t mine = sh[t];
-        uint32_t r = 0;
-        for (uint32_t u = 0; u < n; u++) r += sh[u] < mine ? 1u : 0u;
-        const uint32_t prim = (uint32_t)(mine & 0xffffffffull);
-        const float* b = d.aabb + 6 * (size_t)prim;
-        const size_t j = (size_t)start + r;
-        sidx[j] = prim | (band << PRIM_BITS);
-#pragma unroll
-        for (int c = 0; c < 6; c++) s_aabb[6 * j + c] = b[c];
-        s_lo[j] = b[B.axis];
-    }
-}
 // Binary search of the sorted lower bounds by a whole wavefront: every step probes 64 evenly spaced positions at once, so a range of n entries is
 // narrowed in log64(n) dependent loads instead of log2(n) (a sweep entry spent most of its time in these chains). STRICT: count the
 // entries < v (lower bound), otherwise the entries <= v (upper bound). All lanes return the same index.
@@ -1152,8 +1020,6 @@ struct ContactSystem
     DevBuf<uint32_t> bp_idx, bp_idx_alt;
     DevBuf<float> s_aabb, s_lo;
     DevBuf<uint32_t> bp_cnt, bp_off;
-    DevBuf<uint32_t> bp_hist;   // entries per (class, band) segment | cursors (k_bp_hist / k_bp_scatter)
-    bool seg_sort_ok = true;    // false once a segment exceeded SEG_SORT_MAX entries (counters[58]): the library sort from then on
     DevBuf<int> seg;
     const uint32_t* s_idx = nullptr;
     Bands bands{-1, -1, 0.f, 1.f, 0.f};
@@ -1164,18 +1030,6 @@ struct ContactSystem
     DevBuf<int> counters;  // [0] candidates, [1] intersections, [2] differs, [8..8+N_TABLES] bounds, [48..51] box list (k_bp_fill; [51] = entries needed)
     // result of the last barrier-table search and the inputs it saw (Context::data_version, dt): an identical request is answered from here
     int n_last = 0;  // keys found by the last search (sizes the padded sort of the next one)
-    // The intersection check of a line-search candidate runs the proximity search of the evaluation that follows it, too (same state, same
-    // boxes; one read-back for both): the result waits here until detect_and_route asks for exactly that state.
-    struct Speculated
-    {
-        bool valid = false;
-        uint64_t version = 0;
-        double dt = 0.0;
-        float enl = -1.f;
-        int n = 0;
-        int h[64];
-        const uint64_t* sorted = nullptr;
-    } spec;
     bool cache_valid = false;
     bool ix_valid = false;  // last intersection count (count_intersections)
     uint64_t ix_version = 0;
@@ -1431,8 +1285,7 @@ void choose_axes(Context& c, ContactSystem& cs)
         if (!(var[k] == var[k])) var[k] = 0.0;
     }
     int order[3] = {0, 1, 2};
-    if (c.sweep_axis_by_extent) std::sort(order, order + 3, [&](int a, int b) { return hi[a] - lo[a] > hi[b] - lo[b]; });
-    else std::stable_sort(order, order + 3, [&](int a, int b) { return var[a] > var[b]; });
+    std::stable_sort(order, order + 3, [&](int a, int b) { return var[a] > var[b]; });
     cs.bands.axis = order[0];
     cs.bands.band_axis = order[1];
     const double ext = std::max(hi[order[1]] - lo[order[1]], 1e-12);
@@ -1450,17 +1303,6 @@ void sort_boxes(Context& c, ContactSystem& cs, const ContactDev& d)
     cs.bp_cnt.ensure((size_t)n + 1); cs.bp_off.ensure((size_t)n + 1);
     cs.bp_keys.ensure(cap); cs.bp_keys_alt.ensure(cap); cs.bp_idx.ensure(cap); cs.bp_idx_alt.ensure(cap);
     cs.s_aabb.ensure(6 * (size_t)cap); cs.s_lo.ensure(cap); cs.seg.ensure(3 * NBANDS + 2);
-    if (cs.seg_sort_ok && c.seg_sort) {  // option: three launches instead of the library's sort and the scans around it (see k_seg_sort; measured slower)
-        cs.bp_hist.ensure(2 * (size_t)N_SEG);
-        fill_async(c.stream, cs.bp_hist.p, 0, 2 * (size_t)N_SEG * sizeof(uint32_t));
-        hipLaunchKernelGGL(k_bp_hist, dim3((n + CB - 1) / CB), dim3(CB), 0, c.stream, d, cs.bands, cs.bp_hist.p);
-        hipLaunchKernelGGL(k_bp_scatter, dim3((n + CB - 1) / CB), dim3(CB), 0, c.stream, d, cs.bands, (const uint32_t*)cs.bp_hist.p, cs.bp_hist.p + N_SEG, cs.bp_keys.p, cap,
-                           cs.counters.p + 48);
-        hipLaunchKernelGGL(k_seg_sort, dim3(N_SEG * SEG_PARTS), dim3(SEG_SORT_THREADS), 0, c.stream, d, cs.bands, (const uint32_t*)cs.bp_hist.p, (const uint64_t*)cs.bp_keys.p, cap, cs.bp_idx.p,
-                           cs.s_aabb.p, cs.s_lo.p, cs.seg.p, cs.counters.p + 48);
-        cs.s_idx = cs.bp_idx.p;
-        return;
-    }
     hipLaunchKernelGGL(k_bp_count, dim3((n + 1 + CB - 1) / CB), dim3(CB), 0, c.stream, d, cs.bands, cs.bp_cnt.p);
     size_t tmp = 0;
     MS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cs.bp_cnt.p, cs.bp_off.p, n + 1, c.stream));
@@ -1551,13 +1393,11 @@ bool sharded_search_overflowed(Context& c, ContactSystem& cs, const int* h)
     return true;
 }
 template <bool PROX, bool FR>
-void launch_sweep(Context& c, ContactSystem& cs, const ContactDev& d, double enl2, bool reset_tasks = false)
+void launch_sweep(Context& c, ContactSystem& cs, const ContactDev& d, double enl2)
 {
     cs.sweep_tasks.ensure(3 * (size_t)SWEEP_TASK_CAP + 4);
-    // (the task counter lives among the search's counters, which every caller zeroes before the search: counters[56]; a second sweep behind
-    // the same fill — the speculative proximity search — resets it itself)
+    // (the task counter lives among the search's counters, which every caller zeroes before the search: counters[56])
     int* task_count = cs.counters.p + 56;
-    if (reset_tasks) fill_async(c.stream, task_count, 0, sizeof(int));
     const int pt_on = (int)(cs.pt_enabled && cs.n_t > 0), ee_on = (int)(cs.ee_enabled && cs.n_e > 1);
     const bool sharded = search_is_sharded(c, cs);
     const int W = sharded ? c.world : 1, me = sharded ? c.rank : 0;
@@ -1576,38 +1416,10 @@ int padded_key_count(const ContactSystem& cs)
 }
 // keys[0, n_sort) sorted (n_dev: the count on the device, the rest is padding), table boundaries and "same as the installed list" flag into
 // counters[8..] / counters[2]; returns the sorted list
-// The contact keys of a search (a few thousand, padded to n_sort) sorted in ONE launch: every workgroup stages all keys in LDS tile by tile and
-// every thread counts the keys that sort before its own (equal keys — the padding — by position): its rank is where it goes. The library's radix
-// sort of 64-bit keys took five launches for this.
-constexpr int RANK_SORT_MAX = 16384, RANK_TILE = 4096;
-__global__ __launch_bounds__(CB) void k_rank_sort_keys(const uint64_t* __restrict__ keys, int n, uint64_t* __restrict__ out)
-{
-    __shared__ uint64_t tile[RANK_TILE];
-    const int e = blockIdx.x * CB + threadIdx.x;
-    const uint64_t mine = e < n ? keys[e] : 0ull;
-    int r = 0;
-    for (int t0 = 0; t0 < n; t0 += RANK_TILE) {
-        const int len = min(RANK_TILE, n - t0);
-        __syncthreads();
-        for (int t = threadIdx.x; t < len; t += CB) tile[t] = keys[t0 + t];
-        __syncthreads();
-        // (keys before position e count when <=, keys behind it when <: equal keys keep their order)
-        for (int u = 0; u < len; u++) {
-            const uint64_t k = tile[u];
-            r += (k < mine || (k == mine && t0 + u < e)) ? 1 : 0;
-        }
-    }
-    if (e < n) out[r] = mine;
-}
 const uint64_t* sort_and_bound(Context& c, ContactSystem& cs, int n_sort, const int* n_dev, bool compare)
 {
     hipcub::DoubleBuffer<uint64_t> dk(cs.keys.p, cs.keys_alt.p);
-    // (the one-launch rank sort alone, beside the library's box sort, was measured in round 5: contact callbacks 12 -> 25 ms per 20 iterations —
-    // every thread reads all n keys out of LDS; it stays part of option seg_sort only)
-    if (n_sort > 1 && n_sort <= RANK_SORT_MAX && c.seg_sort) {
-        hipLaunchKernelGGL(k_rank_sort_keys, dim3((n_sort + CB - 1) / CB), dim3(CB), 0, c.stream, (const uint64_t*)cs.keys.p, n_sort, cs.keys_alt.p);
-        dk.selector = 1;
-    } else if (n_sort > 1) {
+    if (n_sort > 1) {
         size_t tmp = 0;
         MS_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, dk, n_sort, 0, 64, c.stream));
         cs.cub_tmp.ensure(tmp);
@@ -1659,14 +1471,7 @@ int64_t detect_and_route(Context& c, double dt, bool friction)
     const uint64_t* sorted = cs.keys.p;
     const bool compare = !friction && cs.n_prev >= 0;
     if (compare) cs.prev.ensure(std::max<size_t>((size_t)cs.n_prev, 1));
-    const bool speculated = !friction && cs.spec.valid && !c.no_contact_cache && !cs.brute_force && cs.spec.version == c.data_version && cs.spec.dt == dt && cs.spec.enl == enl_f;
-    if (speculated) {  // the intersection check of this very state has searched already
-        std::memcpy(h, cs.spec.h, sizeof(h));
-        n = cs.spec.n;
-        sorted = cs.spec.sorted;
-    }
-    cs.spec.valid = false;  // (any search below reuses the key buffers)
-    for (; !speculated;) {
+    for (;;) {
         fill_async(c.stream, cs.counters.p, 0, 64 * sizeof(int));
         // One read-back per search: the key list is sorted over a padded length chosen from the previous search's count (padding keys sort
         // last and carry a table id no table has), the table boundaries are found with the count still on the device, and count,
@@ -1705,11 +1510,6 @@ int64_t detect_and_route(Context& c, double dt, bool friction)
         lap(2);
         n = h[0];
         if (sharded_search_overflowed(c, cs, h)) continue;
-        if (!cs.brute_force && h[58] && cs.seg_sort_ok) {  // a segment of the box list too long for the in-LDS sort: the library sort from now on
-            cs.seg_sort_ok = false;
-            cs.bp_valid = false;
-            continue;
-        }
         if (!cs.brute_force && h[51] > cs.bp_cap) {  // (counters[48 + 3]) the banded box list did not fit: grow and search again
             cs.bp_cap = h[51] + h[51] / 4;
             cs.bp_valid = false;
@@ -1738,7 +1538,7 @@ int64_t detect_and_route(Context& c, double dt, bool friction)
     cs.n_last = n;
     const int* bounds = h + 8;
     const bool unchanged = compare && n == cs.n_prev && h[2] == 0;
-    if (trace) std::fprintf(stderr, "[contact]   searched: n=%d n_prev=%d differs=%d unchanged=%d speculated=%d\n", n, (int)cs.n_prev, h[2], (int)unchanged, (int)speculated);
+    if (trace) std::fprintf(stderr, "[contact]   searched: n=%d n_prev=%d differs=%d unchanged=%d\n", n, (int)cs.n_prev, h[2], (int)unchanged);
     if (unchanged) {
         // the installed tables ARE this state's: the evaluation that opens the next Newton iteration asks again at the same state (round 5: the
         // cache used to be refreshed only by an installation, and every search that found the tables unchanged was followed by a second one)
@@ -1845,35 +1645,14 @@ int64_t count_intersections_uncached(Context& c, double dt)
             cs.keys.ensure(cs.key_cap);
             cs.keys_alt.ensure(cs.key_cap);
         }
-        cs.spec.valid = false;
-        const bool speculate = !c.no_contact_cache && c.contact_speculation;  // (option; off by default)
         for (bool first = true;; first = false) {
             if (!(first && boxes_current)) sort_boxes(c, cs, d);
             cs.bands.shrink = enl_f > 0.f ? 2.f * enl_f * (1.f - 1e-3f) : 0.f;
             launch_sweep<false, false>(c, cs, d, 0.0);
-            // ... and, behind it, the proximity search of the evaluation that follows an accepted candidate (same state, same boxes), up
-            // to the table boundaries: its counts come back with the intersection count, detect_and_route then only routes
-            const uint64_t* sorted = nullptr;
-            int n_pad = 0;
-            if (speculate) {
-                const bool compare = cs.n_prev >= 0;
-                if (compare) cs.prev.ensure(std::max<size_t>((size_t)cs.n_prev, 1));
-                launch_sweep<true, false>(c, cs, d, enl * enl, /*reset_tasks=*/true);
-                merge_sharded_search(c, cs);
-                n_pad = padded_key_count(cs);
-                hipLaunchKernelGGL(k_pad_keys, dim3((n_pad + CB - 1) / CB), dim3(CB), 0, c.stream, cs.keys.p, (const int*)cs.counters.p, n_pad);
-                sorted = sort_and_bound(c, cs, n_pad, (const int*)cs.counters.p, compare);
-            }
-            if (!speculate) merge_sharded_search(c, cs);  // (the ranks' intersection counts; with speculation the merge above carried them)
+            merge_sharded_search(c, cs);  // (the ranks' intersection counts)
             int hb[64];
             fetch(c, hb, cs.counters.p, sizeof(hb));
             if (sharded_search_overflowed(c, cs, hb)) {
-                fill_async(c.stream, cs.counters.p, 0, 64 * sizeof(int));
-                continue;
-            }
-            if (hb[58] && cs.seg_sort_ok) {
-                cs.seg_sort_ok = false;
-                cs.bp_valid = false;
                 fill_async(c.stream, cs.counters.p, 0, 64 * sizeof(int));
                 continue;
             }
@@ -1887,16 +1666,6 @@ int64_t count_intersections_uncached(Context& c, double dt)
             cs.bp_version = c.data_version;
             cs.bp_dt = dt;
             cs.bp_enl = enl_f;
-            if (speculate && (size_t)hb[0] <= cs.key_cap && hb[0] <= n_pad) {
-                cs.spec.valid = true;
-                cs.spec.version = c.data_version;
-                cs.spec.dt = dt;
-                cs.spec.enl = enl_f;
-                cs.spec.n = hb[0];
-                cs.spec.sorted = sorted;
-                std::memcpy(cs.spec.h, hb, sizeof(hb));
-            }
-            if (speculate) cs.n_last = hb[0];
             return hb[1];
         }
     } else {
@@ -2037,10 +1806,6 @@ int cd_search(StandaloneDetector& D, const ContactDev& d, bool proximity, double
             launch_sweep<false, false>(c, cs, d, -1.0);
         }
         fetch(c, h, cs.counters.p, 64 * sizeof(int));
-        if (h[58] && cs.seg_sort_ok) {
-            cs.seg_sort_ok = false;
-            continue;
-        }
         if (h[51] > cs.bp_cap) {
             cs.bp_cap = h[51] + h[51] / 4;
             continue;

@@ -276,8 +276,7 @@ struct Context
 
     int64_t ndofs = 0, nbr = 0;
     DevBuf<double> u, grad, du, r, z, p, q, tmp_a, tmp_b;
-    DevBuf<double> p2;              // second buffer of the search direction (fused direction update: pcg())
-    bool no_fuse_dir = true;        // option "fuse_dir" = 1: the direction update formed inside the SpMV (k_spmv_dir; measured slower, kept as a variant)
+    DevBuf<double> p2;              // second direction-sized buffer (pcg_cg, the sharded solves)
     size_t n_elem_total = 0, hess_total = 0;
     DevBuf<double> elemE, elemH;
     DevBuf<float> elemHf;           // float pool of the lazy potentials
@@ -292,9 +291,7 @@ struct Context
     hipStream_t aux_stream = nullptr;   // the small potentials of an evaluation run beside the large ones (eval())
     hipEvent_t aux_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool no_eval_overlap = false;     // option "no_eval_overlap"
-    bool contact_speculation = false; // option "contact_speculation": the intersection check runs the proximity search of the next evaluation ahead
     bool no_bounded_pattern = false;  // measurement / cross-check: the contact part's pattern with a read-back per stage, like the static part's
-    int kernel_dbg = 0;             // option "kernel_dbg": measurement switches inside kernels (PotArgs::dbg)
     DevBuf<uint8_t> is_projected, active_blocks;
     bool have_hessians = false;
 
@@ -312,7 +309,6 @@ struct Context
     int proj_variant = 0;          // PSD projection, bits: 1 = matrix in LDS (k_project_eig) instead of registers, 2 = no batching of short lists, 4 = IEEE div/sqrt
     int pcg_batch = 0;             // tuning: PCG iterations per launch batch (one batch is always queued ahead of the one the host waits for); 0 = by size
     int spmv_grid_cap = 0;         // tuning: max workgroups of the SpMV kernel (0 = default)
-    int hf_layout = 0;             // float pool of the lazy tets: 0 = pair-major Hf[pair][element][9]; 1 = element-major Hf[element][pair][9] (round 5: measured, 2 % slower overall — the tet kernel's strided stores cost more than the gather gains — kept as an option and cross-check)
     int custom_rtc = 1;            // user-defined potentials: kernels emitted from the op sequence and compiled by hipRTC (0: the device interpreter only)
     int custom_timing = 0;         // measurement: HIP events around every launch of a user-defined potential (synchronises), counter "custom_kernel_us"
     double custom_kernel_us = 0.0;
@@ -321,8 +317,6 @@ struct Context
     int spmv_nt = -1;              // non-temporal loads of the matrix values in the SpMV: -1 = when the matrix is beyond the Infinity Cache, 0 = never, 1 = always
     bool atomic_assembly = false;  // debug switch: scatter with float atomics instead of the deterministic gather
     bool force_generic = false;    // debug switch: evaluate every potential through the generic hyper-dual path
-    bool pcg_holdback = false;     // pcg(): no look-ahead batch while the batch in flight is expected to converge (measured: 1.150 against 1.140 ms per solve, off)
-    bool sweep_axis_by_extent = false;  // contact search: sweep / band axes by the extent of the vertices' bounding box (through round 5) instead of their variance
     bool generic_inertia = false;  // ... EnergyLumpedInertia only (its closed form: k_eval_lumped_inertia)
     bool generic_contact = false;  // ... the contact / friction potentials only (their closed forms: contact_closed.hpp)
     int contact_closed_min_lanes = -1;  // closed forms for tables with at least this many (element, DoF pair) lanes; -1: by potential (launch_eval)
@@ -357,18 +351,6 @@ struct Context
     double* h_scratch = nullptr;    // pinned host scratch
     void* h_pin = nullptr;          // pinned staging area of fetch()
     void* h_stage[2] = {nullptr, nullptr};  // pinned staging areas of h2d_staged() (uploads of the caller's pageable arrays)
-    // Option "pin_host_arrays" (a drop-in's shim turns it on): the caller's large arrays — DoF sets and bound arrays, whose addresses the engine keeps
-    // anyway — are page-locked in place (hipHostRegister, checked) so that transfers to and from them are direct DMA instead of copies through a
-    // staging buffer (4 MB of DoFs to the caller before every callback: 0.2 ms pageable). Registered once per (address, size); released when the
-    // array is rebound / resized and at destruction; a range that cannot be registered stays pageable (ok = false, not retried).
-    struct PinnedRange
-    {
-        size_t bytes = 0;
-        bool ok = false;
-    };
-    std::map<const void*, PinnedRange> pinned;
-    bool pin_host_arrays = false;
-    int64_t n_pin_ok = 0, n_pin_failed = 0;
     void* h_small[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned slots of small uploads of host temporaries (kernels.hip: h2d_small)
     hipEvent_t h_small_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned h_small_next = 0;
@@ -387,39 +369,6 @@ struct Context
     uint32_t pub2_seq = 0;
     // bumped by everything that can change what a contact detection sees (DoFs, bound arrays, layout): the detector skips a search whose
     // inputs are those of its previous one (the evaluation that opens a Newton iteration repeats the accepted line-search state)
-    // a projection round as it travels between its phases (kernels.hip: project_phase_a / _b / _c)
-    struct ProjRound
-    {
-        struct Mark  // what k_proj_mark needs of a potential's list once the eigen-decompositions have run
-        {
-            int pot;
-            const uint32_t* list;
-            int nl;
-            const double* Hc;
-            int n_pool_c;
-        };
-        std::vector<Mark> marks;
-        bool mark_part[2] = {false, false};
-    };
-    // ... and one started ahead of the solve that may need it (project_speculate)
-    struct ProjSpec
-    {
-        bool active = false;
-        int stage = 0;  // 1: phase A queued, counts on their way; 2: phase B queued
-        double threshold = 0.0, eps = 0.0;
-        int mirroring = 0;
-        hipStream_t stream = nullptr;
-        hipEvent_t ev_in = nullptr, ev_done = nullptr;
-        int64_t* pinned = nullptr;  // 128 counters + flag word, coherent host memory
-        uint32_t seq = 0;
-        int64_t h[128];
-        ProjRound round;
-        bool pending = false;  // a request pcg() takes up once its first batches are queued
-        double p_eps = 0.0, p_threshold = 0.0;
-        int p_mirroring = 0;
-    } spec;
-    bool proj_speculation = false;  // option "proj_speculation": the next projection round's selection and eigen kernels run beside the solve (measured: no gain)
-    int64_t n_proj_speculated = 0, n_proj_adopted = 0;
     uint64_t data_version = 1;
     int64_t n_dof_skips_verified = 0;  // MISTARK_VERIFY_DOF_SKIP=1: skipped transfers checked against a real one
     uint64_t u_version = 1, u_host_version = 0;  // the DoF vector on the device / as last brought to the caller's arrays (mistark_dofs_to_host_arrays_if_changed)
@@ -448,7 +397,6 @@ struct Context
     bool no_multi_eval_p = false;
     std::vector<char> multi_p_sent;
     DevBuf<char> multi_p_dev;
-    bool late_eager_assembly = false;  // option (measurement): the static part's gather queued behind the gradient gathers and the join, as through round 4
     bool no_multi_eval_pgh = false;  // option: every contact / friction table in a launch of its own (k_eval_pgh) instead of one shared launch (k_eval_pgh_multi)
     std::vector<char> multi_h_sent;
     DevBuf<char> multi_h_dev;
@@ -489,7 +437,6 @@ struct Context
                 n_prelaunch_dropped++;
             }
     }
-    bool seg_sort = false;          // option "seg_sort": the contact search's box list and key list sorted by the engine's own kernels (k_seg_sort, k_rank_sort_keys: measured slower)
     bool no_sharded_search = false; // option "no_sharded_search": every rank of a sharded problem sweeps all candidate pairs itself (cross-check)
     bool no_contact_cache = false;  // option "no_contact_cache": every detection request runs the search (cross-check)
     size_t h_scratch_n = 0;
@@ -497,7 +444,6 @@ struct Context
     // SpMV timing
     bool time_spmv = false;
     std::vector<hipEvent_t> ev;
-    std::vector<hipEvent_t> pcg_ev;  // batch completion events of the PCG driver
     std::vector<hipEvent_t> stage_ev;  // stage marks of newton_solve (GPU-side stage times without synchronising)
     double spmv_ms_sum = 0.0;
     double spmv_empty_ms_sum = 0.0;  // empty event brackets recorded right behind the sampled launches
@@ -586,9 +532,6 @@ void fetch(Context& c, void* dst_host, const void* src_dev, size_t bytes);
 // the range inside every copy (1.5 ms for 4 MB measured); a memcpy into pinned memory and a DMA transfer take a quarter of that. The source
 // may be reused when the call returns; the copy is ordered on c.stream like any other.
 void h2d_staged(Context& c, void* dst_dev, const void* src_host, size_t bytes);
-// option pin_host_arrays: is [host, host + bytes) page-locked (registering it now if it is large enough and not yet known)?
-bool host_range_pinned(Context& c, const void* host, size_t bytes);
-void host_range_unpin(Context& c, const void* host);
 // fills and device-to-device copies as kernels of our own (kernels.hip: the runtime's blit path costs the host 10-25 us per call); a FillQueue
 // collects up to FILL_BATCH_MAX regions (4-byte aligned, multiples of 4 bytes) into ONE launch: add(), add(), ..., flush()
 constexpr int FILL_BATCH_MAX = 8;
@@ -634,13 +577,6 @@ void contact_shared_rows(Context& c, std::vector<int32_t>& rows);  // contact.hi
 int register_potential(Context& c, const char* name, const int32_t* conn, int32_t n_elem, int32_t conn_stride, const mistark_binding* bindings, int32_t n_bindings);
 void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_abs = nullptr, bool lazy = false);
 void reduce_dot_and_max_abs(Context& c, const double* a, const double* b, int64_t n, double* dot, double* max_abs_a);
-bool project_can_speculate(const Context& c);
-void project_speculate(Context& c, double eps, int mirroring, double threshold, bool ev_in_recorded = false);
-void project_speculate_request(Context& c, double eps, int mirroring, double threshold);
-void project_speculate_pending(Context& c);
-void project_spec_poll(Context& c);
-bool project_spec_adopt(Context& c, double eps, int mirroring, double threshold, int* all_active, int64_t* n_projected_now);
-void project_spec_discard(Context& c);
 void project(Context& c, double eps, int mirroring, const uint8_t* active_host, bool by_gradient, double threshold, int* all_active,
              int64_t* n_projected_now, int64_t* n_changed_now);
 void assemble(Context& c);

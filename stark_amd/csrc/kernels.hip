@@ -352,7 +352,6 @@ struct TetEarlyOut
         const PotArgs& A = *a;
         const int pe = pool_of(A, le);
         elemE[pe] = energy_here(A, e) ? E : 0.0;
-        if (A.dbg & 1) return;  // measurement switch: no gradient output
         if (A.gpool) {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -419,7 +418,7 @@ struct TetBlockFloatSink
     float* stage;     // [64 * 9] of this wavefront
     float* Hwave;     // pool position of the wavefront's first element (pair 0); 16-byte aligned (pool stride is a multiple of 64 elements)
     size_t hstride;   // floats between pair pools
-    int lane, n_valid, dbg;
+    int lane, n_valid;
     __device__ __forceinline__ void put(int a, int b, const double* blk)
     {
 #pragma unroll
@@ -428,17 +427,7 @@ struct TetBlockFloatSink
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         float* dst = Hwave + (size_t)tet_pair_index(a, b) * hstride;
-        if (dbg & 2) {  // measurement switch: no global stores
-        } else if (dbg & 4) {
-            // ELEMENT-major pool Hf[element][pair][9] (option hf_layout = 1): the ten blocks of a tet are 360 contiguous bytes, so the blocks a
-            // BSR tile gathers — those of the few dozen tets around its rows' nodes — share cache lines instead of lying in ten pair pools.
-            // A wavefront's stores of one pair are 36-byte pieces 360 bytes apart; its ten puts fill the same lines within the kernel.
-            if (lane < n_valid) {
-                float* d = Hwave + ((size_t)lane * 10 + tet_pair_index(a, b)) * 9;
-#pragma unroll
-                for (int c = 0; c < 9; c++) d[c] = stage[lane * 9 + c];
-            }
-        } else if (n_valid == 64) {
+        if (n_valid == 64) {
             const float4* s4 = reinterpret_cast<const float4*>(stage);
             float4* d4 = reinterpret_cast<float4*>(dst);
             d4[lane] = s4[lane];
@@ -479,7 +468,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void
         TetBlockStagedSink sink{early, MODE == TET_PGH, stage + wave * 9 * 64, elemH + (size_t)pe_wave * 9, (size_t)a.n_pool * 9, lane, min(64, a.e_count - le_wave)};
         tet_closed_eval_to<FULL>(in, E, g, sink, true);
     } else if (MODE == TET_PGH_F) {
-        TetBlockFloatSink sink{early, reinterpret_cast<float*>(stage) + wave * 9 * 64, elemHf + (size_t)pe_wave * ((a.dbg & 4) ? 90 : 9), (size_t)a.n_pool * 9, lane, min(64, a.e_count - le_wave), a.dbg};
+        TetBlockFloatSink sink{early, reinterpret_cast<float*>(stage) + wave * 9 * 64, elemHf + (size_t)pe_wave * 9, (size_t)a.n_pool * 9, lane, min(64, a.e_count - le_wave)};
         tet_closed_eval_to<FULL>(in, E, g, sink, true);
     } else {
         tet_closed_eval<FULL>(in, E, g, nullptr, 0, false);
@@ -680,7 +669,7 @@ static void dyn_grad_gather(Context& c, double* grad)
 }
 static void launch_grad_gather(Context& c, Potential& P)
 {
-    if (!P.args.gpool || P.dyn_pool || (c.kernel_dbg & 1)) return;  // (dyn_pool: one gather for all device-resident tables, dyn_grad_gather)
+    if (!P.args.gpool || P.dyn_pool) return;  // (dyn_pool: one gather for all device-resident tables, dyn_grad_gather)
     hipLaunchKernelGGL(k_grad_gather, dim3(grid_for(3 * c.nbr)), dim3(BLOCK), 0, c.stream, (const double*)P.gpool.p, (const uint32_t*)P.inc_start.p, (const uint32_t*)P.inc.p, c.nbr,
                        c.grad.p);
     if (P.n_inc_long > 0)
@@ -836,7 +825,6 @@ static void launch_tet_closed(Context& c, Potential& P, int mode, bool kernel_on
     } else if (c.lazy_active) {
         PotArgs A = P.args;
         A.n_pool = P.n_pool_f;
-        if (c.hf_layout) A.dbg |= 4;  // element-major float pool
         hipLaunchKernelGGL((k_eval_tet_closed<En, FULL, TET_PGH_F>), g, b, 0, c.stream, A, E, (double*)nullptr, c.elemHf.p + P.hf_off, c.grad.p);
     } else {
         hipLaunchKernelGGL((k_eval_tet_closed<En, FULL, TET_PGH>), g, b, 0, c.stream, P.args, E, c.elemH.p + P.h_off, (float*)nullptr, c.grad.p);
@@ -1170,40 +1158,9 @@ static bool publish(Context& c, void* dst_host, const void* src_dev, size_t byte
     std::memcpy(dst_host, c.pub, bytes);
     return true;
 }
-bool host_range_pinned(Context& c, const void* host, size_t bytes)
-{
-    constexpr size_t MIN_BYTES = (size_t)128 << 10;  // (below: HIP's own staging path costs less than a registration is worth)
-    if (!c.pin_host_arrays || c.dry || !host || bytes < MIN_BYTES) return false;
-    auto it = c.pinned.find(host);
-    if (it != c.pinned.end()) {
-        if (it->second.bytes == bytes) return it->second.ok;
-        if (it->second.ok) (void)hipHostUnregister(const_cast<void*>(host));  // (the same address at another size: registered anew)
-        (void)hipGetLastError();
-        c.pinned.erase(it);
-    }
-    const hipError_t e = hipHostRegister(const_cast<void*>(host), bytes, hipHostRegisterDefault);
-    if (e != hipSuccess) (void)hipGetLastError();  // (overlaps another registration, not the caller's to lock, limits: the range stays pageable)
-    c.pinned[host] = Context::PinnedRange{bytes, e == hipSuccess};
-    (e == hipSuccess ? c.n_pin_ok : c.n_pin_failed)++;
-    return e == hipSuccess;
-}
-void host_range_unpin(Context& c, const void* host)
-{
-    auto it = c.pinned.find(host);
-    if (it == c.pinned.end()) return;
-    if (it->second.ok) {
-        (void)hipHostUnregister(const_cast<void*>(host));  // (the caller may have freed the range already: the error is not ours to report)
-        (void)hipGetLastError();
-    }
-    c.pinned.erase(it);
-}
 void h2d_staged(Context& c, void* dst_dev, const void* src_host, size_t bytes)
 {
     constexpr size_t CHUNK = (size_t)4 << 20;
-    if (host_range_pinned(c, src_host, bytes)) {  // page-locked in place: one direct transfer
-        MS_CHECK(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c.stream));
-        return;
-    }
     if (bytes < ((size_t)1 << 16)) {  // (small: HIP copies these through its own staging buffer without pinning anything)
         MS_CHECK(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c.stream));
         return;
@@ -1892,7 +1849,6 @@ void prepare(Context& c)
             A.n_pool = P.n_elem;
             A.elem_list = nullptr;
             A.lrow = nullptr;
-            A.dbg = c.kernel_dbg;
             A.e_begin = 0;
             A.e_count = P.n_elem;
             P.n_key = P.n_elem;
@@ -2009,7 +1965,7 @@ void prepare(Context& c)
             e_off += (size_t)P.n_key;
             P.n_pool_f = (P.n_key + 63) / 64 * 64;
             // (a lazy potential's share of the double pool is unused while the lazy path is on — except as the compact pool of its projection
-            // rounds, project_phase_b: whole wavefronts of 64 elements, hence the rounding)
+            // rounds, project_selected: whole wavefronts of 64 elements, hence the rounding)
             h_off += (size_t)(P.lazy_capable ? P.n_pool_f : P.n_key) * 9 * P.NB * P.NB;
             P.hf_off = hf_off;
             if (P.lazy_capable) hf_off += (size_t)P.n_pool_f * 9 * 10;
@@ -2174,7 +2130,7 @@ static void evt_collect(Context& c)  // (the previous evaluation's stamps: all o
 void eval_prelaunch(Context& c, int mode, bool lazy)
 {
     Context::EvalPre& pre = c.pre[mode == MISTARK_EVAL_P ? 0 : 1];
-    if (c.no_eval_prelaunch || c.no_eval_overlap || c.layout_dirty || c.force_generic || c.kernel_dbg || c.dry || pre.valid) return;
+    if (c.no_eval_prelaunch || c.no_eval_overlap || c.layout_dirty || c.force_generic || c.dry || pre.valid) return;
     const bool lazy_active = mode == MISTARK_EVAL_P_G_H && lazy && !c.atomic_assembly && c.hf_total > 0;
     if (mode == MISTARK_EVAL_P_G_H && (c.elemH.cap < std::max<size_t>(c.hess_total, 1) || c.elemHf.cap < std::max<size_t>(lazy_active ? c.hf_total : 0, 16))) return;  // (first evaluation: eval() allocates)
     if (c.elemE.cap < std::max<size_t>(c.n_elem_total, 1)) return;
@@ -2292,7 +2248,6 @@ void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_a
     // sit behind every gradient gather and the join, and 150-180 us of the 275 us gather ended up in front of the linear solve).
     c.static_assembled = false;
     const bool eager_asm = split && mode == MISTARK_EVAL_P_G_H && lazy && !c.atomic_assembly && !c.no_eager_assembly && !c.part[0].dirty && c.part[0].nnzb > 0;
-    const bool early_asm = eager_asm && !c.late_eager_assembly;
     std::vector<Potential*> deferred_gathers;
     auto static_assembly = [&]() {
         if (!c.aux_ev[2]) {
@@ -2324,13 +2279,13 @@ void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_a
         MultiFirst mf;
         mf.n = 0;
         int multi_blocks = 0;
-        const bool batch_p = mode == MISTARK_EVAL_P && c.world == 1 && !c.no_multi_eval_p && !c.kernel_dbg;
+        const bool batch_p = mode == MISTARK_EVAL_P && c.world == 1 && !c.no_multi_eval_p;
         // energy + gradient + Hessian: the contact and friction tables share one launch (k_eval_pgh_multi)
         std::vector<MultiPGH> multi_h;
         MultiFirst mfh;
         mfh.n = 0;
         int multi_h_blocks = 0;
-        const bool batch_h = mode == MISTARK_EVAL_P_G_H && c.world == 1 && !c.no_multi_eval_pgh && !c.kernel_dbg;
+        const bool batch_h = mode == MISTARK_EVAL_P_G_H && c.world == 1 && !c.no_multi_eval_pgh;
         hipStream_t multi_h_stream = main_stream;
         double* multi_h_grad = grad_main;
         for (auto& P : c.pots) {
@@ -2381,7 +2336,7 @@ void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_a
                         if (mode != MISTARK_EVAL_P)  // the energies it wrote aside (the line search's energy evaluation summed elemE meanwhile)
                             copy_async(c.stream, c.elemE.p + P.e_off, c.elemE_pre.p + P.e_off, (size_t)P.args.e_count * sizeof(double));
                         if (mode == MISTARK_EVAL_P) {
-                        } else if (early_asm) deferred_gathers.push_back(&P);
+                        } else if (eager_asm) deferred_gathers.push_back(&P);
                         else if (P.name == E_TetStrain::name) launch_tet_closed<E_TetStrain, true>(c, P, mode, false, true);
                         else launch_tet_closed<E_TetStrainEO, false>(c, P, mode, false, true);
                         taken = true;
@@ -2389,7 +2344,7 @@ void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_a
                     }
                 if (taken) continue;
             }
-            if (early_asm && !aux && !c.force_generic && P.kind != KIND_CUSTOM && (P.name == E_TetStrain::name || P.name == E_TetStrainEO::name)) {
+            if (eager_asm && !aux && !c.force_generic && P.kind != KIND_CUSTOM && (P.name == E_TetStrain::name || P.name == E_TetStrainEO::name)) {
                 // the kernel now, its gradient gather behind the event the static assembly waits for (below)
                 if (P.name == E_TetStrain::name) launch_tet_closed<E_TetStrain, true>(c, P, mode, true);
                 else launch_tet_closed<E_TetStrainEO, false>(c, P, mode, true);
@@ -2431,7 +2386,7 @@ void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_a
     c.grad.p = grad_main;
     if (split) MS_CHECK(hipEventRecord(c.aux_ev[1], c.aux_stream));  // (the join below waits for the small potentials, not for the gather queued behind them)
     if (split && mode == MISTARK_EVAL_P_G_H && c.evt_armed[0]) evt_mark(c, 2, c.aux_stream);
-    if (early_asm) {
+    if (eager_asm) {
         static_assembly();
         for (Potential* P : deferred_gathers) {
             if (P->name == E_TetStrain::name) launch_tet_closed<E_TetStrain, true>(c, *P, mode, false, true);
@@ -2443,8 +2398,7 @@ void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_a
         vec_axpby(c, c.grad.p, 1.0, c.grad.p, 1.0, c.grad_aux.p, c.ndofs);
     }
     // the device-resident tables' node gradients (contact, friction), row by row in sorted order: behind everything else, one addition per row
-    if (mode != MISTARK_EVAL_P && !(c.kernel_dbg & 1)) dyn_grad_gather(c, c.grad.p);
-    if (eager_asm && !early_asm) static_assembly();  // (option late_eager_assembly: where it sat through round 4, for A/B runs)
+    if (mode != MISTARK_EVAL_P) dyn_grad_gather(c, c.grad.p);
     // (the contact part's pattern ends in a read-back of its counts, for which the host waits: the energy / residual reductions of THIS stream
     // are queued first where they do not depend on it, so that they run while the host waits — see with_max below)
     bool pattern_pending = overlap_pattern;

@@ -32,7 +32,6 @@ struct PotArgs
     // An element's energy counts on the rank that owns the row of its first DoF block.
     const int32_t* lrow;
     int n_own;
-    int dbg;                  // measurement switches (option "kernel_dbg"; results are wrong when set)
     int dof_col[MAX_NB];      // connectivity column providing the node of local DoF block k
     int dof_row_off[MAX_NB];  // first block row of the DoF set of local DoF block k
     // Gradient rows of SMALL DoF sets (a handful of rigid bodies touched by tens of thousands of contacts) are not accumulated in place:

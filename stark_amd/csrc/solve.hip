@@ -52,7 +52,7 @@ __device__ __forceinline__ uint32_t make_desc(uint32_t kp, const DescRange* __re
             if (r.lazy) {
                 const uint32_t a = ab / r.NB, b = ab - a * r.NB;
                 const uint32_t pr = (uint32_t)(a > b ? tet_pair_index((int)b, (int)a) : tet_pair_index((int)a, (int)b));
-                d = DESC_FLOAT | (a > b ? DESC_TRANS : 0u) | (r.lazy == 2u ? r.pool_blk + e * 10u + pr : r.pool_blk + pr * r.n_pool + e);  // (2: element-major pool)
+                d = DESC_FLOAT | (a > b ? DESC_TRANS : 0u) | (r.pool_blk + pr * r.n_pool + e);
             } else {
                 d = r.pool_blk + ab * r.n_pool + e;
             }
@@ -460,7 +460,7 @@ static void make_descriptors(Context& c, int part)
         const bool lazy = c.lazy_active && P.lazy_capable;
         // (key space and pools hold the n_key elements this context evaluates: all of them, or the rank's list)
         rg.push_back(DescRange{(uint32_t)P.kp_off, (uint32_t)P.n_key, (uint32_t)P.NB, 0u, (uint32_t)P.n_key, lazy ? (uint32_t)(P.hf_off / 9) : (uint32_t)P.k_off,
-                               lazy ? (uint32_t)P.n_pool_f : (uint32_t)P.n_key, lazy ? (c.hf_layout ? 2u : 1u) : 0u});
+                               lazy ? (uint32_t)P.n_pool_f : (uint32_t)P.n_key, lazy ? 1u : 0u});
     }
     if (c.hess_total / 9 > DESC_MASK || c.hf_total / 9 > DESC_MASK) throw Error("element-Hessian pool too large for the gather descriptors");
     m.sorted_desc.ensure(m.n_keys);
@@ -487,7 +487,7 @@ void gather_part(Context& c, int part, const uint8_t* only_dirty)
     const uint32_t* desc = m.sorted_desc.p;
     // the whole static part from the lazy float pool, one GPU: blocks that are each other's transposes are summed once (k_sym_classify)
     const uint32_t* sym = nullptr;
-    if (part == 0 && !only_dirty && c.world == 1 && c.lazy_active && !c.no_sym_gather && !c.hf_layout && m.n_keys > 0) {
+    if (part == 0 && !only_dirty && c.world == 1 && c.lazy_active && !c.no_sym_gather && m.n_keys > 0) {
         if (!m.sym_valid) {
             m.sym.ensure((size_t)m.nnzb);
             hipLaunchKernelGGL(k_sym_classify, dim3(grid_for(m.nnzb)), dim3(BLOCK), 0, c.stream, m.slot_start.p, desc, m.colw.p, m.slot_row.p, m.row_ptr.p, m.nnzb, store, m.sym.p);
@@ -572,11 +572,8 @@ __device__ __forceinline__ double dpp_row_shr(double v)
 // x gather, the nine float -> double conversions and FMAs of the reference (BlockedSparseMatrix.h:986-1138), then a segmented inclusive
 // scan over the 64 lanes (DPP row shifts + three scalar carries, no LDS) whose row-end lanes write y; a row that continues into the next
 // tile of the chunk is carried in registers. Every row is written exactly once: no atomics, no zero fill, deterministic.
-// What the SpMV multiplies with. XPlain: a vector in memory. XDir: the PCG's search direction p = z + beta p_old computed on the fly, so that
-// the direction update needs no kernel of its own (k_pcg_dir: one launch, one dependent-kernel boundary and 12 MB of vector traffic per
-// iteration at 1M tets); the lane that finishes a row also stores p[row] for k_pcg_step and the next iteration. MEASURED (configs[3],
-// profiles/r02_v2_fuse_dir_kernel_stats.txt): the second gathered vector costs the SpMV 8 us (23.9 -> 32), more than the 7.3 us kernel it
-// replaces (1.40 instead of 1.32 ms per solve); identical iteration counts. Kept as option "fuse_dir" and as a cross-check of the solver.
+// What the SpMV multiplies with: a vector in memory (XSoA below: measurement only). Forming the PCG's direction p = z + beta p_old on the fly
+// instead (no k_pcg_dir launch) lost: the second gathered vector cost the SpMV more than the kernel it replaced.
 struct XPlain
 {
     const double* x;
@@ -597,45 +594,6 @@ struct XPlain
         p2 = pd[r3 + 2];
     }
     __device__ __forceinline__ double row_dot_pre(size_t, double p0, double p1, double p2, double y0, double y1, double y2) const { return p0 * y0 + p1 * y1 + p2 * y2; }
-};
-struct XDir
-{
-    const double* z;
-    const double* pold;
-    double* pnew;
-    double beta;
-    __device__ __forceinline__ void load(size_t c3, double& x0, double& x1, double& x2) const
-    {
-        x0 = z[c3] + beta * pold[c3];
-        x1 = z[c3 + 1] + beta * pold[c3 + 1];
-        x2 = z[c3 + 2] + beta * pold[c3 + 2];
-    }
-    __device__ __forceinline__ bool has_dot() const { return true; }
-    // the row's own entries of p: stored (every block row ends in exactly one lane of the static part), and p[row] . y[row] for p.Ap
-    __device__ __forceinline__ double row_dot(size_t r3, double y0, double y1, double y2) const
-    {
-        double p0, p1, p2;
-        load(r3, p0, p1, p2);
-        pnew[r3] = p0;
-        pnew[r3 + 1] = p1;
-        pnew[r3 + 2] = p2;
-        return p0 * y0 + p1 * y1 + p2 * y2;
-    }
-    __device__ __forceinline__ void row_pre(size_t r3, double& p0, double& p1, double& p2) const { load(r3, p0, p1, p2); }
-    __device__ __forceinline__ double row_dot_pre(size_t r3, double p0, double p1, double p2, double y0, double y1, double y2) const
-    {
-        pnew[r3] = p0;
-        pnew[r3 + 1] = p1;
-        pnew[r3 + 2] = p2;
-        return p0 * y0 + p1 * y1 + p2 * y2;
-    }
-    // (contact part: its rows are stored by the static part; here only the product is needed)
-    __device__ __forceinline__ double row_dot_nostore(size_t r3, double y0, double y1, double y2) const
-    {
-        double p0, p1, p2;
-        load(r3, p0, p1, p2);
-        return p0 * y0 + p1 * y1 + p2 * y2;
-    }
 };
 __device__ __forceinline__ double row_dot_nostore(const XPlain& X, size_t r3, double y0, double y1, double y2) { return X.row_dot(r3, y0, y1, y2); }
 // Measurement only (spmv_variant 12; north_star names "SoA node/DoF arrays"): the vectors as three arrays x[n], y[n], z[n] instead of the
@@ -662,7 +620,6 @@ struct XSoA
     __device__ __forceinline__ double row_dot_pre(size_t, double p0, double p1, double p2, double y0, double y1, double y2) const { return p0 * y0 + p1 * y1 + p2 * y2; }
 };
 __device__ __forceinline__ double row_dot_nostore(const XSoA& X, size_t r3, double y0, double y1, double y2) { return X.row_dot(r3, y0, y1, y2); }
-__device__ __forceinline__ double row_dot_nostore(const XDir& X, size_t r3, double y0, double y1, double y2) { return X.row_dot_nostore(r3, y0, y1, y2); }
 
 // v_mov_b32_dpp on both halves; BOUND: lanes without a source receive 0, otherwise (and in rows the mask disables) 0 as well (old = 0)
 template <int CTRL, int ROW_MASK, bool BOUND>
@@ -1066,71 +1023,6 @@ __global__ __launch_bounds__(BLOCK) void k_to_soa(const double* __restrict__ v, 
     out[2 * n + i] = v[3 * i + 2];
 }
 #endif
-// The PCG's iteration k as the solver launches it: what k_pcg_dir did for iteration k-1 (sums of r.r and r.z, convergence test, beta) in the
-// prologue of every workgroup (all of them compute the same numbers from the same partial sums; workgroup 0 records them), then
-// q = A p with p = z + beta p_old formed on the fly and stored by the lanes that finish a row.
-struct DirArgs
-{
-    const double* z;
-    const double* pold;
-    double* pnew;
-    const double* part_rr;
-    const double* part_rz;
-    int nparts, k;
-    double abs_tol, rel_tol;
-};
-// convergence test and beta from the partial sums step k-1 left; returns false when the solve is over (and records why)
-__device__ __forceinline__ bool pcg_direction(const DirArgs& a, PcgCtrl* __restrict__ ctrl, double* sm, double& beta)
-{
-    const int done = ctrl->done;
-    if (done == 1) return false;
-    if (done == 2) {  // indefiniteness stop decided in k_pcg_step of the previous iteration
-        if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->done = 1;
-        return false;
-    }
-    beta = 0.0;
-    if (a.k == 1) return true;  // p_1 = z_0
-    const int kp = a.k - 1;     // the iteration whose step left the partial sums
-    const double rr = sum_partials(a.part_rr, a.nparts, sm);
-    const double rz_new = sum_partials(a.part_rz, a.nparts, sm);
-    const double error = sqrt(rr / ctrl->bb);
-    const bool conv = error < a.abs_tol || error / 1.0 < a.rel_tol;  // error_0 = 1 for x0 = 0
-    if (conv) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            ctrl->error = error;
-            ctrl->n_iter = kp;
-            ctrl->converged = 1;
-            ctrl->done = 1;
-        }
-        return false;
-    }
-    beta = rz_new / ctrl->rz[kp & 1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctrl->rz[(kp + 1) & 1] = rz_new;
-        ctrl->error = error;
-        ctrl->n_iter = kp;
-    }
-    return true;
-}
-__global__ __launch_bounds__(BLOCK) void k_spmv_dir(int g0, int gr, int g1, StaticPart m, DynPart d, DirArgs a, double* __restrict__ y, double* __restrict__ partials,
-                                                   PcgCtrl* __restrict__ ctrl)
-{
-    __shared__ double sm[4];
-    double beta;
-    if (!pcg_direction(a, ctrl, sm, beta)) return;
-    const int b = (int)blockIdx.x;
-    const XDir X{a.z, a.pold, a.pnew, beta};
-    if (b < g1) spmv_chunks(b, g1, d, X, partials + g0 + gr);
-    else if (b < g1 + gr) spmv_long_rows(b - g1, gr, m.vals, m.scol, m.long_rows, m.n_long_rows, m.row_ptr, m.row_pos, X, y, partials + g0);
-    else spmv_chunked_static<0>(b - g1 - gr, g0, m.vals, m.scol, m.tile_first_row, m.n_chunks, m.chunk_tiles, X, y, partials);
-}
-// the same test at the end of a batch of iterations (the host looks at the control block there)
-__global__ __launch_bounds__(BLOCK) void k_pcg_check(DirArgs a, PcgCtrl* __restrict__ ctrl)
-{
-    __shared__ double sm[4];
-    double beta;
-    (void)pcg_direction(a, ctrl, sm, beta);
-}
 __global__ __launch_bounds__(BLOCK) void k_spmv_combine(int64_t nbr, const int32_t* __restrict__ crow_of_row, const uint32_t* __restrict__ row_chunk0,
                                                        const double* __restrict__ yd, const double* __restrict__ chunk_partial, double* __restrict__ y)
 {
@@ -1175,22 +1067,6 @@ if (nt) hipLaunchKernelGGL(k_spmv_fused<4>, dim3(g0 + gr + g1), dim3(BLOCK), 0, 
     if (g1 > 0 && combine)
         hipLaunchKernelGGL(k_spmv_combine, dim3(grid_for(c.mrows())), dim3(BLOCK), 0, c.stream, c.mrows(), (const int32_t*)m1.crow_of_row.p, (const uint32_t*)m1.row_chunk0.p,
                            (const double*)m1.yd.p, (const double*)m1.chunk_partial.p, y);
-    return g0 + gr + g1;
-}
-static int launch_spmv_dir(Context& c, const DirArgs& a, double* y, double* partials)
-{
-    const BsrPart& m0 = c.part[0];
-    BsrPart& m1 = c.part[1];
-    const int g0 = spmv_grid(c, m0.n_chunks_static, MAX_PARTIALS / 2);
-    const int gr = std::min(((m0.n_long_rows + 3) / 4 + 7) / 8 * 8, MAX_PARTIALS / 4);
-    const StaticPart sp{m0.vals.p, m0.scol.p, m0.tile_first_row.p, m0.long_rows.p, m0.row_ptr.p, m0.row_pos.p, m0.n_chunks_static, m0.n_long_rows, m0.chunk_tiles};
-    DynPart d{};
-    int g1 = 0;
-    if (m1.nnzb > 0) {
-        g1 = (int)std::min<int64_t>(((m1.n_chunks + 3) / 4 + (m1.n_rows + BLOCK / 4 - 1) / (BLOCK / 4) + 7) / 8 * 8, MAX_PARTIALS / 4);
-        d = DynPart{m1.vals.p, m1.colw.p, m1.row_ptr.p, m1.row_chunk0.p, m1.chunk_row.p, m1.rowmap.p, m1.yd.p, m1.chunk_partial.p, m1.n_chunks, m1.n_rows};
-    }
-    hipLaunchKernelGGL(k_spmv_dir, dim3(g0 + gr + g1), dim3(BLOCK), 0, c.stream, g0, gr, g1, sp, d, a, y, partials, c.ctrl.p);
     return g0 + gr + g1;
 }
 #ifdef MISTARK_BENCH_VARIANTS
@@ -2406,13 +2282,6 @@ void fused_pcg_replay(Context& c, int n_launches, double* s_us, double* v_us)
     if (v_us) *v_us = 1e3 * ms[1] / n_launches;
 }
 
-__global__ void k_copy_ctrl(const PcgCtrl* __restrict__ src, PcgCtrl* __restrict__ dst_host)
-{
-    if (threadIdx.x == 0) {
-        *dst_host = *src;
-        __threadfence_system();
-    }
-}
 static double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // ---- option "cg_variant" = 1 on ONE GPU: the Chronopoulos-Gear iteration of the sharded solve without the windows -----------------------------
 // Two launches per iteration instead of three: S (the solver's SpMV on u = M^-1 r, partial w.u) and V (k_cg_vec in its local mode: every
@@ -2533,21 +2402,18 @@ void pcg(Context& c, const double* rhs_dev, double abs_tol, double rel_tol, int 
     double* part_rr = c.partials.p + MAX_PARTIALS;
     double* part_rz = c.partials.p + 2 * MAX_PARTIALS;
     double* part_bb = c.partials.p + 3 * MAX_PARTIALS;
-    const bool fuse_dir = !c.no_fuse_dir;
-    c.p2.ensure((size_t)c.ndofs);
     // (solver numbering: the solution accumulates in a scratch vector and is written to c.du in the caller's numbering at the end)
     if (c.perm_active) c.xl.ensure((size_t)c.ndofs);
     double* const xs = c.perm_active ? c.xl.p : c.du.p;
-    // (fused: iteration 1 reads p_0 = buffer 0 with beta = 0; k_pcg_init leaves z there, so 0 * p_0 is finite)
     {
         const BsrPart& d1 = c.part[1];
         hipLaunchKernelGGL(k_pcg_prologue, dim3(gv), dim3(BLOCK), 0, c.stream, rhs_dev, rhs_scale, (const float*)c.part[0].vals.p, (const int32_t*)c.diag_slot[0].p,
-                           d1.nnzb ? (const float*)d1.vals.p : (const float*)nullptr, (const int32_t*)c.diag_slot[1].p, c.nbr, c.dinv.p, xs, c.r.p, c.z.p, fuse_dir ? c.p2.p : c.p.p,
+                           d1.nnzb ? (const float*)d1.vals.p : (const float*)nullptr, (const int32_t*)c.diag_slot[1].p, c.nbr, c.dinv.p, xs, c.r.p, c.z.p, c.p.p,
                            part_bb, part_rz, c.perm_active ? (const int32_t*)c.iperm.p : (const int32_t*)nullptr);
     }
     hipLaunchKernelGGL(k_pcg_init2, dim3(1), dim3(BLOCK), 0, c.stream, part_bb, part_rz, gv, abs_tol, c.ctrl.p, 1);
-    // Iterations are launched in batches of PCG_BATCH; after each batch the control block is copied to a pinned slot and an
-    // event recorded. The host launches batch b+1 BEFORE it waits for batch b's event, so the GPU never idles on the host's
+    // Iterations are launched in batches of PCG_BATCH; the last iteration of a batch writes the control block to a pinned slot.
+    // The host launches batch b+1 BEFORE it waits for batch b's slot, so the GPU never idles on the host's
     // convergence check, and at most one batch of device-side no-op launches (ctrl->done) is wasted after convergence.
     constexpr int PCG_BATCH_MAX = 8;  // (sizes of the sampling buffers)
     // (option "pcg_batch"; 0 = by size: 3 for the large systems, whose iterations are long enough for the host to keep up with shorter batches and
@@ -2555,11 +2421,6 @@ void pcg(Context& c, const double* rhs_dev, double abs_tol, double rel_tol, int 
     // = 1.145 / 1.140 / 1.155 / 1.176 —, 4 for the small ones, whose 13 us iterations the host barely outruns: configs[0] 254 against 244-248)
     const int PCG_BATCH = std::min(std::max(c.pcg_batch > 0 ? c.pcg_batch : (c.nbr >= 100000 ? 3 : 4), 1), PCG_BATCH_MAX);
     PcgCtrl* hs[2] = {reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048), reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048 + 64)};  // pinned
-    while (c.pcg_ev.size() < 2) {
-        hipEvent_t e;
-        MS_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c.pcg_ev.push_back(e);
-    }
     const int epoch = ++c.pcg_epoch;
     std::vector<int> sampled[2];
     int clk_grid[2] = {0, 0};
@@ -2583,45 +2444,29 @@ void pcg(Context& c, const double* rhs_dev, double abs_tol, double rel_tol, int 
                 }
                 MS_CHECK(hipEventRecord(c.ev[e0], c.stream));
             }
-            // p_k = z + beta p_{k-1} lives in buffer k & 1 (the SpMV forms it on the fly and stores it)
-            double* pk = (k & 1) ? c.p.p : c.p2.p;
-            const double* pprev = (k & 1) ? c.p2.p : c.p.p;
-            int gs;
-            if (fuse_dir) {
-                gs = launch_spmv_dir(c, DirArgs{c.z.p, pprev, pk, part_rr, part_rz, gv, k, abs_tol, rel_tol}, c.q.p, part_pq);
-            } else {
-                pk = c.p.p;
-                uint64_t* clk = nullptr;
-                if (sample) {
-                    if (!c.spmv_clk) MS_CHECK(hipHostMalloc((void**)&c.spmv_clk, sizeof(uint64_t) * 2 * PCG_BATCH_MAX * 2 * MAX_PARTIALS, hipHostMallocDefault));
-                    clk = c.spmv_clk + ((size_t)slot * PCG_BATCH_MAX + sampled[slot].size()) * 2 * MAX_PARTIALS;
-                    std::memset(clk, 0, sizeof(uint64_t) * 2 * MAX_PARTIALS);
-                }
-                gs = launch_spmv<0>(c, c.p.p, c.q.p, c.p.p, part_pq, c.ctrl.p, /*combine=*/false, clk);
-                if (sample) clk_grid[slot] = gs;
-            }
+            uint64_t* clk = nullptr;
             if (sample) {
+                if (!c.spmv_clk) MS_CHECK(hipHostMalloc((void**)&c.spmv_clk, sizeof(uint64_t) * 2 * PCG_BATCH_MAX * 2 * MAX_PARTIALS, hipHostMallocDefault));
+                clk = c.spmv_clk + ((size_t)slot * PCG_BATCH_MAX + sampled[slot].size()) * 2 * MAX_PARTIALS;
+                std::memset(clk, 0, sizeof(uint64_t) * 2 * MAX_PARTIALS);
+            }
+            const int gs = launch_spmv<0>(c, c.p.p, c.q.p, c.p.p, part_pq, c.ctrl.p, /*combine=*/false, clk);
+            if (sample) {
+                clk_grid[slot] = gs;
                 MS_CHECK(hipEventRecord(c.ev[e0 + 1], c.stream));
                 // an empty bracket right behind: what a pair of event records costs the stream by itself (the marker packets' own processing
                 // is inside every bracketed duration; bench.py reports both figures)
                 MS_CHECK(hipEventRecord(c.ev[e0 + 2], c.stream));
                 sampled[slot].push_back(k);
             }
-            hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(BLOCK), 0, c.stream, k, stop_on_indef, part_pq, gs, c.dinv.p, c.nbr, (const double*)pk, c.q.p, xs, c.r.p, c.z.p, part_rr,
+            hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(BLOCK), 0, c.stream, k, stop_on_indef, part_pq, gs, c.dinv.p, c.nbr, (const double*)c.p.p, c.q.p, xs, c.r.p, c.z.p, part_rr,
                                part_rz, c.ctrl.p, dyn ? (const int32_t*)m1.crow_of_row.p : nullptr, (const uint32_t*)m1.row_chunk0.p, (const double*)m1.yd.p,
                                (const double*)m1.chunk_partial.p);
-            if (!fuse_dir)
-                hipLaunchKernelGGL(k_pcg_dir, dim3(gv), dim3(BLOCK), 0, c.stream, k, abs_tol, rel_tol, part_rr, part_rz, gv, c.ndofs, c.z.p, c.p.p, c.ctrl.p, 1,
-                                   k == k_end ? hs[slot] : (PcgCtrl*)nullptr, epoch);
+            hipLaunchKernelGGL(k_pcg_dir, dim3(gv), dim3(BLOCK), 0, c.stream, k, abs_tol, rel_tol, part_rr, part_rz, gv, c.ndofs, c.z.p, c.p.p, c.ctrl.p, 1,
+                               k == k_end ? hs[slot] : (PcgCtrl*)nullptr, epoch);
         }
-        // (fused: the test of the batch's last iteration would only run with the next batch's first SpMV; the host reads the control block now)
-        if (fuse_dir) hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(BLOCK), 0, c.stream, DirArgs{c.z.p, nullptr, nullptr, part_rr, part_rz, gv, k_end + 1, abs_tol, rel_tol}, c.ctrl.p);
         // the control block reaches the pinned slot from the batch's last k_pcg_dir itself (round 1: a copy command on another engine, 4 us
-        // + a 5.6 us gap; then a one-wavefront copy kernel, 4 us + its boundary, every four iterations); the fused variant still copies
-        if (fuse_dir) {
-            hipLaunchKernelGGL(k_copy_ctrl, dim3(1), dim3(64), 0, c.stream, (const PcgCtrl*)c.ctrl.p, hs[slot]);
-            MS_CHECK(hipEventRecord(c.pcg_ev[slot], c.stream));
-        }
+        // + a 5.6 us gap; then a one-wavefront copy kernel, 4 us + its boundary, every four iterations)
         return k_end;
     };
     auto drain = [&](int slot, int last_real_iter) {
@@ -2654,62 +2499,39 @@ void pcg(Context& c, const double* rhs_dev, double abs_tol, double rel_tol, int 
     PcgCtrl* h = nullptr;
     int slot = 0;
     int k_end_cur = launch_batch(0);
-    // The look-ahead batch is held back when the batch in flight is expected to converge: from the errors the last two finished batches
-    // reported, error_b ~ error_{b-1} * (error_{b-1} / error_{b-2}). A converged solve then wastes the rest of ONE batch instead of that
-    // plus a whole batch of no-op launches (4 to 7 iterations of three launches each were 4 % of a solve); a wrong guess costs one host
-    // round trip with the GPU idle. Same iterations either way. MEASURED on configs[3] (tools/ab_option.sh pcg_holdback 3): 1.150 ms per solve
-    // with it, 1.140 without — the no-op launches are 2 us each and the wrong guesses cost as much as the right ones save: option pcg_holdback,
-    // off by default.
-    const double tol = std::max(abs_tol, rel_tol);
-    double err1 = 1.0, err2 = -1.0;  // batch-end errors, newest first (error_0 = 1)
     for (;;) {
         const bool more = k <= max_iter;
-        int k_end_next = 0;
-        bool hold = false;
-        if (more && c.pcg_holdback && !fuse_dir) {
-            const double shrink = err2 > 0.0 ? std::min(1.0, std::max(0.02, err1 / err2)) : 0.5;
-            hold = err1 * shrink < tol;
-        }
-        if (more && !hold) k_end_next = launch_batch(slot ^ 1);  // keep the GPU fed while the host looks at the previous batch
-        project_speculate_pending(c);  // (a projection round to run beside this solve: queued behind the solve's first batches)
-        if (fuse_dir) {
-            MS_CHECK(hipEventSynchronize(c.pcg_ev[slot]));
-        } else {
-            const volatile PcgCtrl* v = hs[slot];
-            const double t_wait = now_seconds();
-            auto reported = [&] { return v->epoch == epoch && (v->done || v->n_iter >= k_end_cur); };
-            for (uint64_t spins = 0; !reported(); spins++) {
-                __builtin_ia32_pause();
-                if ((spins & 0x3f) == 0) project_spec_poll(c);  // (a projection round started ahead of this solve: its second phase once its counts are here)
-                if ((spins & 0xfffff) != 0xfffff) continue;
-                // now and then a real look at the stream, as publish() does: a failed launch surfaces as its error, and a stream that has
-                // drained without the slot being written (host memory the device's writes do not reach while kernels run) is answered from
-                // the device's own control block instead of a time-out
-                const hipError_t q = hipStreamQuery(c.stream);
-                if (q != hipErrorNotReady) {
-                    MS_CHECK(q);
-                    if (!reported()) {
-                        PcgCtrl dev{};
-                        MS_CHECK(hipMemcpy(&dev, c.ctrl.p, sizeof(PcgCtrl), hipMemcpyDeviceToHost));
-                        hs[slot]->converged = dev.converged;
-                        hs[slot]->indef = dev.indef;
-                        hs[slot]->error = dev.error;
-                        hs[slot]->n_iter = dev.done ? dev.n_iter : k_end_cur;
-                        hs[slot]->done = dev.done ? 1 : 0;
-                        hs[slot]->epoch = epoch;
-                    }
-                    break;
+        const int k_end_next = more ? launch_batch(slot ^ 1) : 0;  // keep the GPU fed while the host looks at the previous batch
+        const volatile PcgCtrl* v = hs[slot];
+        const double t_wait = now_seconds();
+        auto reported = [&] { return v->epoch == epoch && (v->done || v->n_iter >= k_end_cur); };
+        for (uint64_t spins = 0; !reported(); spins++) {
+            __builtin_ia32_pause();
+            if ((spins & 0xfffff) != 0xfffff) continue;
+            // now and then a real look at the stream, as publish() does: a failed launch surfaces as its error, and a stream that has
+            // drained without the slot being written (host memory the device's writes do not reach while kernels run) is answered from
+            // the device's own control block instead of a time-out
+            const hipError_t q = hipStreamQuery(c.stream);
+            if (q != hipErrorNotReady) {
+                MS_CHECK(q);
+                if (!reported()) {
+                    PcgCtrl dev{};
+                    MS_CHECK(hipMemcpy(&dev, c.ctrl.p, sizeof(PcgCtrl), hipMemcpyDeviceToHost));
+                    hs[slot]->converged = dev.converged;
+                    hs[slot]->indef = dev.indef;
+                    hs[slot]->error = dev.error;
+                    hs[slot]->n_iter = dev.done ? dev.n_iter : k_end_cur;
+                    hs[slot]->done = dev.done ? 1 : 0;
+                    hs[slot]->epoch = epoch;
                 }
-                if (now_seconds() - t_wait > 60.0) throw Error("pcg: the device did not report batch " + std::to_string(k_end_cur) + " within 60 s");
+                break;
             }
-            std::atomic_thread_fence(std::memory_order_acquire);
+            if (now_seconds() - t_wait > 60.0) throw Error("pcg: the device did not report batch " + std::to_string(k_end_cur) + " within 60 s");
         }
+        std::atomic_thread_fence(std::memory_order_acquire);
         h = hs[slot];
         if (c.time_spmv) drain(slot, h->done ? h->n_iter : k_end_cur);
         if (h->done || !more) break;
-        err2 = err1;
-        err1 = h->error;
-        if (hold) k_end_next = launch_batch(slot ^ 1);  // (the guess fell short)
         slot ^= 1;
         k_end_cur = k_end_next;
     }
@@ -2749,13 +2571,9 @@ Context::~Context()
         if (h_small[k]) (void)hipHostFree(h_small[k]);
         if (h_small_ev[k]) (void)hipEventDestroy(h_small_ev[k]);
     }
-    for (auto& kv : pinned)  // (option pin_host_arrays: the caller's arrays are the caller's again)
-        if (kv.second.ok) (void)hipHostUnregister(const_cast<void*>(kv.first));
-    (void)hipGetLastError();
     for (hipEvent_t e : evt)  // (MISTARK_EVAL_EVENTS marks, kernels.hip evt_mark)
         if (e) (void)hipEventDestroy(e);
     for (auto e : ev) (void)hipEventDestroy(e);
-    for (auto e : pcg_ev) (void)hipEventDestroy(e);
     for (auto e : stage_ev) (void)hipEventDestroy(e);
     if (h_scratch) (void)hipHostFree(h_scratch);
     if (h_pin) (void)hipHostFree(h_pin);
@@ -2772,11 +2590,6 @@ Context::~Context()
         (void)hipStreamDestroy(side_stream);
         (void)hipEventDestroy(side_ev[0]);
         (void)hipEventDestroy(side_ev[1]);
-    }
-    if (spec.stream) {  // (= pre_stream, destroyed above)
-        (void)hipEventDestroy(spec.ev_in);
-        (void)hipEventDestroy(spec.ev_done);
-        (void)hipHostFree(spec.pinned);
     }
     if (stream && owns_stream) (void)hipStreamDestroy(stream);
 }

@@ -254,7 +254,7 @@ def test_cloth_on_box_contact_trajectory(closed_forms, monkeypatch):
                                           # repeated-search caches): the reference's iteration counts either way
                                           ("traj_cfg3_blockbox_10", "no_eval_overlap"), ("traj_cfg3_blockbox_10", "no_bounded_pattern"),
                                           ("traj_cfg3_blockbox_10", "no_pattern_overlap"), ("traj_cfg3_blockbox_10", "no_contact_cache"),
-                                          ("traj_cfg3_blockbox_10", "contact_speculation"), ("traj_cfg3_blockbox_10", "no_eager_assembly"),
+                                          ("traj_cfg3_blockbox_10", "no_eager_assembly"),
                                           # every contact / friction table through the closed-form kernels (contact_closed.hpp; by default only
                                           # tables long enough to pay), and the evaluation not started ahead of the contact callback
                                           ("traj_cfg3_blockbox_10", "contact_closed_min_lanes"), ("traj_blockbox_3", "contact_closed_min_lanes"),
@@ -1059,40 +1059,6 @@ def test_contact_free_runs_are_bit_reproducible():
     assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
 
 
-def test_page_locked_caller_arrays_change_nothing_but_the_transfer_path(monkeypatch):
-    """Engine option pin_host_arrays (round 6; the shim's MISTARK_SHIM_PIN=1): the caller's large DoF and bound arrays are page-locked where they
-    are (checked hipHostRegister), transfers to and from them are direct; released with the context. Same Newton / CG counts and the same bits
-    as with pageable arrays, and the counter says that ranges were really locked. (The mirror keeps its state host-side with
-    mirror_state_to_host: DoFs come back and state arrays go up at every step — the paths the option changes.)"""
-    import ctypes as C
-
-    from stark_amd import sim as S
-
-    def run(pin):
-        monkeypatch.setenv("MISTARK_OPTIONS", "pin_host_arrays=1" if pin else "")
-        st = S.default_settings()
-        st.init_frictional_contact = 0
-        st.mirror_state_to_host = 1
-        sim = S.Simulation(st)
-        cloth = sim.add_surface_grid("cloth", (1.0, 1.0), (96, 96), S.cotton_fabric())     # 9409 nodes: arrays of 226 KB
-        sim.prescribe_inside_aabb(cloth, (0.5, 0.5, 0.0), (0.001, 0.001, 0.001), 1e3)
-        sim.prescribe_inside_aabb(cloth, (0.5, -0.5, 0.0), (0.001, 0.001, 0.001), 1e3)
-        for _ in range(4):
-            assert sim.run_one_step()
-        n = C.c_int64()
-        sim.L.mistark_get_counter.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
-        assert sim.L.mistark_get_counter(sim.engine_handle(), b"host_ranges_pinned", C.byref(n)) == 0
-        i = sim.info()
-        out = (sim.points("x0").copy(), sim.points("v0").copy(), i.total_newton_iterations, i.total_cg_iterations, n.value)
-        sim.close()
-        return out
-
-    a, b = run(False), run(True)
-    assert a[4] == 0 and b[4] >= 1, (a[4], b[4])
-    assert a[2] == b[2] > 4 and a[3] == b[3]
-    assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
-
-
 @pytest.mark.parametrize("grid", [(10, 10, 10)])
 def test_contact_runs_are_bit_reproducible(grid):
     """The same with frictional contact and a rigid body: a soft block on a fixed rigid box (device contact detection, barrier and friction
@@ -1144,43 +1110,3 @@ def test_evaluation_started_ahead_of_the_contact_callback_changes_no_bit():
     a, b = run(0), run(1)
     assert a[2:] == b[2:] and a[2] > 4
     assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
-
-
-def test_projection_round_started_beside_the_solve_changes_no_bit():
-    """Option proj_speculation (kernels.hip: project_speculate): progressive projection retries a failed solve with the rows above the NEXT
-    threshold projected, and that round's selection and eigen-projections can run on another stream while the solve runs; a failed solve adopts
-    them (only the ordered matrix update is left), a successful one drops them. Same selection, same projected blocks, same gather order: the
-    run has the bits of the default path. The scene must take retries for the option to mean anything: the beam of `traj_tetbeam_big_progressive`
-    (start velocities of 40 m/s: 9 linear solves in the 7 Newton iterations of its first step) — and the engine's counters must say that rounds
-    WERE started beside solves and WERE taken over by retries (with the block-on-box scene used before, no solve ever failed).
-    (Measured slower than the default on configs[3], hence an option: DESIGN.md section 8, "Round 4".)"""
-    import ctypes as C
-
-    from stark_amd import capi
-    from stark_amd import sim as S
-
-    def run(on):
-        st = S.default_settings()
-        st.init_frictional_contact = 0
-        sim = S.Simulation(st)
-        ps = sim.add_volume_grid("beam", (0, 0, 0), (4.0, 1.0, 1.0), (8, 2, 2), S.soft_rubber())
-        sim.prescribe_inside_aabb(ps, (-2.0, 0, 0), (2e-3, 2.0, 2.0), 1e7)
-        n = sim.points("v0").shape[0]
-        sim.set_points("v0", 40.0 * np.sin(1.3 * (3.0 * np.arange(n)[:, None] + np.arange(3)[None, :]) + 0.7))
-        sim.prepare()
-        assert capi.lib().mistark_set_option(sim.engine_handle(), b"proj_speculation", on) == 0
-        for _ in range(3):
-            assert sim.run_one_step()
-        i = sim.info()
-        spec, adopted = C.c_int64(), C.c_int64()
-        assert capi.lib().mistark_get_counter(sim.engine_handle(), b"proj_speculated", C.byref(spec)) == 0
-        assert capi.lib().mistark_get_counter(sim.engine_handle(), b"proj_adopted", C.byref(adopted)) == 0
-        out = (sim.points("x0").copy(), sim.points("v0").copy(), i.total_newton_iterations, i.total_linear_solves, i.total_cg_iterations, spec.value, adopted.value)
-        sim.close()
-        return out
-
-    a, b = run(0), run(1)
-    assert a[2:5] == b[2:5] and a[2:4] == (15, 19)                      # the reference's counts (fixture traj_tetbeam_big_progressive)
-    assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
-    # the feature under test did run: rounds were started beside solves and failed solves took them over (and never with the option off)
-    assert a[5:] == (0, 0) and b[5] > 0 and b[6] > 0, (a[5:], b[5:])

@@ -83,6 +83,17 @@ def test_unknown_option_and_null_context(ctx):
     assert L.mistark_set_option(h, b"no_eval_overlap", 1) == 0
     assert L.mistark_set_option(None, b"no_eval_overlap", 1) < 0
     assert L.mistark_last_error(None) == b"null context"
+    # the variants that lost their A/B measurements are gone with their options and counters
+    for name in (b"fuse_dir", b"pcg_holdback", b"proj_speculation", b"contact_speculation", b"seg_sort", b"sweep_axis_by_extent",
+                 b"late_eager_assembly", b"hf_layout", b"kernel_dbg", b"pin_host_arrays"):
+        assert L.mistark_set_option(h, name, 1) < 0, name
+    for name in (b"no_eval_overlap", b"spmv_grid_cap", b"cg_variant"):
+        assert L.mistark_set_option(h, name, 0) == 0, name
+    L.mistark_get_counter.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+    v = C.c_int64()
+    for name in (b"proj_speculated", b"proj_adopted", b"host_ranges_pinned", b"host_ranges_not_pinned"):
+        assert L.mistark_get_counter(h, name, C.byref(v)) < 0, name
+    assert L.mistark_get_counter(h, b"multi_pgh_launches", C.byref(v)) == 0
 
 
 def test_scene_facade_rejects_bad_handles_and_indices():
