@@ -349,7 +349,8 @@ int mistark_sync(mistark_ctx* ctx);
  * "multi_pgh_launches" (evaluations whose contact / friction tables shared one launch; option no_multi_eval_pgh = 1: one launch per table),
  * "contact_searches" / "contact_repeated_searches" (barrier-table searches that ran on the device / that ran at the state the previous one had
  * searched: 0 unless the option no_contact_cache is set), "eval_pgh_issue_us" / "eval_pgh_wait_us" (host microseconds of the P+g+H evaluations:
- * issuing their launches / waiting for their read-backs). */
+ * issuing their launches / waiting for their read-backs), "ccd_queries" / "ccd_skipped_pairs" / "ccd_capped_pairs" (mistark_contact_max_step: queries,
+ * candidate pairs skipped because they touch at the line search's start, pairs whose additive CCD stopped at its iteration cap). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

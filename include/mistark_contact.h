@@ -63,6 +63,13 @@ int mistark_contact_update_friction(mistark_ctx* ctx, int64_t* n_contacts);
 /* Number of intersecting edge-triangle pairs at x0 + dt v1. */
 int mistark_contact_count_intersections(mistark_ctx* ctx, double dt, int64_t* n_found);
 
+/* Continuous collision detection: largest fraction t in (0, 1] of the current Newton direction along which no collision pair's distance falls
+ * below (1 - conservative_rescaling) of its distance at the line search's start (additive CCD on linear vertex trajectories: positions x0 + dt v1
+ * at the engine's DoFs u and at u + du; rigid-body rotation is linearised between the two). Meaningful inside a max_allowed_step callback.
+ * Returns 1 when collisions are disabled or nothing moves. A sharded context returns an error. n_candidates: pairs whose swept boxes overlap
+ * (nullable). Leaves the installed tables and the detection caches alone. */
+int mistark_contact_max_step(mistark_ctx* ctx, double dt, double conservative_rescaling, double* max_step, int64_t* n_candidates);
+
 /* Parity access: rows of one table (by potential name, e.g. "contact_d_d_pt_pt_cubic"); conn == NULL queries n_rows/stride. */
 int mistark_contact_get_table(mistark_ctx* ctx, const char* potential, int32_t* conn, int32_t* n_rows, int32_t* stride);
 /* Parity access: friction data of one friction table: T [n x 6], mu [n], fn [n], bary [n x nbary] (nullable outputs). */

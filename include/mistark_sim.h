@@ -173,6 +173,13 @@ int mistark_sim_contact_group(mistark_sim* sim, int kind, int idx);
 int mistark_sim_set_friction(mistark_sim* sim, int group_a, int group_b, double mu);
 int mistark_sim_disable_collision(mistark_sim* sim, int group_a, int group_b);
 int mistark_sim_get_contact_info(mistark_sim* sim, double* contact_stiffness, int64_t* n_contacts, int64_t* n_friction_contacts, int64_t* n_detections);
+/* Continuous collision detection (off by default; not in the reference): enabled, every Newton line search is bounded so that no collision
+ * pair's distance falls below (1 - conservative_rescaling) of its start value along the step (one max_allowed_step callback calling
+ * mistark_contact_max_step; rigid-body rotation linearised). Off, no callback is registered. */
+int mistark_sim_set_contact_ccd(mistark_sim* sim, int enabled, double conservative_rescaling);
+/* CCD counters of the simulation: queries, queries that limited the step, candidate pairs of the last query, pairs skipped because they touch
+ * at a line search's start, pairs stopped at the iteration cap, seconds spent in the queries (nullable outputs) */
+int mistark_sim_get_ccd_info(mistark_sim* sim, int64_t* n_queries, int64_t* n_limited, int64_t* last_candidates, int64_t* n_skipped, int64_t* n_capped, double* seconds);
 
 /* multi-GPU sharding (mistark.h): every rank builds the same scene, then one of these before the first step */
 int mistark_sim_set_dist_rccl(mistark_sim* sim, int rank, int world, const char unique_id[128]);

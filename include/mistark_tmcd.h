@@ -58,6 +58,11 @@ int mistark_cd_get_broad_phase(mistark_cd* cd, int list, int32_t* rows);
 /* IntersectionDetection::run(): number of intersecting (edge, triangle) pairs; their rows with mistark_cd_get_intersections */
 int mistark_cd_run_intersection(mistark_cd* cd, int32_t* n_pairs);
 int mistark_cd_get_intersections(mistark_cd* cd, int32_t* rows);
+/* Continuous collision detection from the kept positions (xm of every mesh) to x1 (one array per mesh, layout of xm), vertices moving on straight
+ * lines: toi = the largest fraction t in (0, 1] of that motion along which no active, non-blacklisted point-triangle or edge-edge pair's distance
+ * falls below (1 - conservative_rescaling) of its start value (additive CCD, minimum distance 0; 1 = no such pair). Pairs that touch at the
+ * start are left to the intersection test. n_candidates: pairs whose swept boxes overlap. For a STARK application's add_max_allowed_step. */
+int mistark_cd_run_ccd(mistark_cd* cd, const double* const* x1, double conservative_rescaling, double* toi, int32_t* n_candidates);
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,7 @@ def lib():
     L.mistark_contact_update.argtypes = [p, C.c_double, C.POINTER(i64)]
     L.mistark_contact_update_friction.argtypes = [p, C.POINTER(i64)]
     L.mistark_contact_count_intersections.argtypes = [p, C.c_double, C.POINTER(i64)]
+    L.mistark_contact_max_step.argtypes = [p, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)]
     L.mistark_contact_get_table.argtypes = [p, C.c_char_p, p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.mistark_contact_get_friction_data.argtypes = [p, C.c_char_p, p, p, p, p, C.POINTER(C.c_int32)]
     L.mistark_contact_get_vertices.argtypes = [p, p, C.POINTER(i64)]
@@ -330,6 +331,16 @@ class CollisionDetector:
         if n.value:
             self._ck(self.L.mistark_cd_get_intersections(self.h, rows.ctypes.data))
         return rows
+
+    def run_ccd(self, x1, conservative_rescaling=0.9):
+        """mistark_cd_run_ccd: (toi, n_candidates) of the straight-line motion from the kept positions to x1 (one array per mesh)."""
+        import numpy as np
+        self.L.mistark_cd_run_ccd.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        ends = [np.ascontiguousarray(x, dtype=np.float64) for x in x1]
+        ptrs = (C.c_void_p * max(len(ends), 1))(*[x.ctypes.data for x in ends])
+        toi, n = C.c_double(), C.c_int32()
+        self._ck(self.L.mistark_cd_run_ccd(self.h, ptrs, conservative_rescaling, C.byref(toi), C.byref(n)))
+        return toi.value, n.value
 
     def close(self):
         if self.h:

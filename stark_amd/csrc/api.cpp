@@ -566,6 +566,9 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "eval_pgh_wait_us") *out = (int64_t)(1e6 * c.t_eval_wait);
     else if (n == "contact_searches") *out = contact_searches(c, false);
     else if (n == "contact_repeated_searches") *out = contact_searches(c, true);
+    else if (n == "ccd_queries") *out = contact_ccd_counter(c, 0);
+    else if (n == "ccd_skipped_pairs") *out = contact_ccd_counter(c, 1);
+    else if (n == "ccd_capped_pairs") *out = contact_ccd_counter(c, 2);
     else throw Error("mistark_get_counter: unknown counter '" + n + "'");
     API_END(0)
 }

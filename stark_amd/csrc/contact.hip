@@ -181,6 +181,9 @@ struct ContactDev
     // overlap (broad_extra = its enlargement, AABBs.cpp:38) — instead of classifying them
     int broad_only;
     float broad_extra;
+    // ccd (ccd_query): the sweep runs over swept boxes and emits every pair whose boxes overlap (exclusions applied, no distance filter, nearly
+    // parallel edges kept)
+    int ccd;
 };
 struct TableDev
 {
@@ -312,6 +315,10 @@ __device__ __forceinline__ void narrow_pt(const ContactDev& d, int p, int t, dou
     if (d.disabled[mp * d.n_mesh + mt]) return;
     for (int k = 0; k < d.n_bl_pt; k++)  // BroadPhasePTEEBase.cpp:181-205
         if (d.bl_pt[4 * k] <= t && t < d.bl_pt[4 * k + 1] && d.bl_pt[4 * k + 2] <= p && p < d.bl_pt[4 * k + 3]) return;
+    if (d.ccd) {
+        push_key(pack_key(0, 0, 0, p, t), keys, counters, key_cap);
+        return;
+    }
     if (d.broad_only) {  // BroadPhasePTEEBase.cpp:190-214: the pair itself
         const int vt[3] = {v0, v1, v2};
         if (ref_boxes_overlap(d, &p, 1, vt, 3)) push_key(pack_key(0, 0, 0, p, t), keys, counters, key_cap);
@@ -335,6 +342,10 @@ __device__ __forceinline__ void narrow_ee(const ContactDev& d, int ea, int eb, d
     for (int k = 0; k < d.n_bl_ee; k++) {  // (the pair is looked up as (lower, higher) global edge: BroadPhasePTEEBase.cpp:229-258)
         const int lo = ea < eb ? ea : eb, hi = ea < eb ? eb : ea;
         if (d.bl_ee[4 * k] <= lo && lo < d.bl_ee[4 * k + 1] && d.bl_ee[4 * k + 2] <= hi && hi < d.bl_ee[4 * k + 3]) return;
+    }
+    if (d.ccd) {  // (the sweep packs edge pairs lower edge first)
+        push_key(pack_key(1, 1, 0, ea, eb), keys, counters, key_cap);
+        return;
     }
     if (d.broad_only) {  // BroadPhasePTEEBase.cpp:236-262 (the parallel-edge cutoff belongs to the narrow phase)
         const int va[2] = {a0, a1}, vb[2] = {b0, b1};
@@ -982,10 +993,225 @@ __global__ __launch_bounds__(CB) void k_route(ContactDev d, const uint64_t* __re
     T.mu[row] = d.mu[A.mesh * d.n_mesh + B.mesh];
     T.fn[row] = kptr[0] * (dhat - dist) * (dhat - dist);  // _barrier_force, cubic barrier (:1238-1242)
 }
+
+// ---- continuous collision detection (ccd_query) ---------------------------------------------------------------------------------------
+// Vertices move on straight lines from xa (the line search's start) to xb (the full step). Candidates are the pairs whose swept boxes overlap;
+// the narrow phase is additive CCD (Li, Kaufman, Jiang 2021, "Codimensional Incremental Potential Contact", Alg. 1; the IPC toolkit's
+// additive_ccd with minimum distance 0): advance by eta d / l_p until the distance falls below (1 - eta) of its start value. Every advance is a
+// lower bound of the time of impact, so the t it reports never passes the first contact of the linear trajectories.
+constexpr int CCD_MAX_ITERATIONS = 10000;
+// slots of ContactSystem::ccd_counters besides those of a search ([0] candidate pairs, [48..51] box list, [56] sweep tasks)
+constexpr int CCD_N_SURV = 16, CCD_N_SKIPPED = 17, CCD_N_CAPPED = 18, CCD_TOI = 20;  // (CCD_TOI: two ints, the bits of a double)
+// deformable: x0 + dt v; rigid body: integrate_loc_point as k_contact_vertices (rotation linearised between the two end points)
+__global__ __launch_bounds__(CB) void k_ccd_vertices(ContactDev d, const double* __restrict__ x0, const double* __restrict__ v1, const double* __restrict__ dv1,
+                                                    const double* __restrict__ xloc, const double* __restrict__ rb_v1, const double* __restrict__ drb_v1,
+                                                    const double* __restrict__ rb_w1, const double* __restrict__ drb_w1, const double* __restrict__ rb_t0,
+                                                    const double* __restrict__ rb_q0, double dt, double* __restrict__ xa, double* __restrict__ xb)
+{
+    const int i = blockIdx.x * CB + threadIdx.x;
+    if (i >= d.n_v) return;
+    const int m = d.cv_mesh[i], s = d.cv_src[i];
+    if (d.mesh_kind[m] == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double v = v1[3 * s + k];
+            xa[3 * i + k] = x0[3 * s + k] + dt * v;
+            xb[3 * i + k] = x0[3 * s + k] + dt * (v + (dv1 ? dv1[3 * s + k] : 0.0));
+        }
+        return;
+    }
+    const int b = d.mesh_idx[m];
+    const V3<double> xl(xloc[3 * s], xloc[3 * s + 1], xloc[3 * s + 2]);
+    auto place = [&](const double* dv, const double* dw, double* X) {
+        const V3<double> w(rb_w1[3 * b] + (dw ? dw[3 * b] : 0.0), rb_w1[3 * b + 1] + (dw ? dw[3 * b + 1] : 0.0), rb_w1[3 * b + 2] + (dw ? dw[3 * b + 2] : 0.0));
+        const V3<double> r = rb_R1(rb_q0 + 4 * b, w, dt) * xl;
+        X[3 * i] = r.x + (rb_t0[3 * b] + dt * (rb_v1[3 * b] + (dv ? dv[3 * b] : 0.0)));
+        X[3 * i + 1] = r.y + (rb_t0[3 * b + 1] + dt * (rb_v1[3 * b + 1] + (dv ? dv[3 * b + 1] : 0.0)));
+        X[3 * i + 2] = r.z + (rb_t0[3 * b + 2] + dt * (rb_v1[3 * b + 2] + (dv ? dv[3 * b + 2] : 0.0)));
+    };
+    place(nullptr, nullptr, xa);
+    place(drb_v1, drb_w1, xb);
+}
+// swept boxes: float, rounded outwards (as k_contact_aabbs), over both end points, no enlargement; points, triangles, edges
+__global__ __launch_bounds__(CB) void k_ccd_aabbs(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, float* __restrict__ aabb)
+{
+    const int i = blockIdx.x * CB + threadIdx.x;
+    const int n = d.n_v + d.n_t + d.n_e;
+    if (i >= n) return;
+    int v[3], nv;
+    if (i < d.n_v) {
+        v[0] = i;
+        nv = 1;
+    } else if (i < d.n_v + d.n_t) {
+        const int t = i - d.n_v;
+        v[0] = d.tri[3 * t]; v[1] = d.tri[3 * t + 1]; v[2] = d.tri[3 * t + 2];
+        nv = 3;
+    } else {
+        const int e = i - d.n_v - d.n_t;
+        v[0] = d.edge[2 * e]; v[1] = d.edge[2 * e + 1];
+        nv = 2;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        double lo = xa[3 * v[0] + k], hi = lo;
+        for (int j = 0; j < nv; j++) {
+            const double p = xa[3 * v[j] + k], q = xb[3 * v[j] + k];
+            lo = p < lo ? p : lo;
+            hi = p > hi ? p : hi;
+            lo = q < lo ? q : lo;
+            hi = q > hi ? q : hi;
+        }
+        aabb[6 * (size_t)i + k] = __double2float_rd(lo);
+        aabb[6 * (size_t)i + 3 + k] = __double2float_ru(hi);
+    }
+}
+__device__ __forceinline__ double point_segment_sq(const D3& p, const D3& e0, const D3& e1)
+{
+    const D3 e = e1 - e0;
+    const double ee = sq3(e);
+    double t = ee > 0.0 ? dot3(p - e0, e) / ee : 0.0;
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    return sq3(p - (e0 + t * e));
+}
+// one pair: point x[0] and triangle x[1..3], or edge x[0..1] and edge x[2..3]; dx = displacement minus the pair's mean displacement
+struct CcdPair
+{
+    D3 x[4], dx[4];
+    int ee;
+};
+__device__ __forceinline__ CcdPair ccd_pair(const ContactDev& d, uint64_t key, const double* __restrict__ xa, const double* __restrict__ xb)
+{
+    CcdPair P;
+    const int a = (int)((key >> PRIM_BITS) & ((1u << PRIM_BITS) - 1)), b = (int)(key & ((1u << PRIM_BITS) - 1));
+    P.ee = (int)((key >> 57) & 1);
+    int v[4];
+    if (!P.ee) {
+        v[0] = a; v[1] = d.tri[3 * b]; v[2] = d.tri[3 * b + 1]; v[3] = d.tri[3 * b + 2];
+    } else {
+        v[0] = d.edge[2 * a]; v[1] = d.edge[2 * a + 1]; v[2] = d.edge[2 * b]; v[3] = d.edge[2 * b + 1];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        P.x[k] = ldx(xa, v[k]);
+        P.dx[k] = ldx(xb, v[k]) - P.x[k];
+    }
+    const D3 mean = 0.25 * (((P.dx[0] + P.dx[1]) + P.dx[2]) + P.dx[3]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) P.dx[k] = P.dx[k] - mean;
+    return P;
+}
+// l_p: largest displacement on one side plus the largest on the other
+__device__ __forceinline__ double ccd_lp(const CcdPair& P)
+{
+    const double s0 = sq3(P.dx[0]), s1 = sq3(P.dx[1]), s2 = sq3(P.dx[2]), s3 = sq3(P.dx[3]);
+    if (!P.ee) return ::sqrt(s0) + ::sqrt(fmax(s1, fmax(s2, s3)));
+    return ::sqrt(fmax(s0, s1)) + ::sqrt(fmax(s2, s3));
+}
+// the classified distances of the proximity search; (nearly) parallel edges — which that search drops and a CCD must keep — take the
+// smallest of the four point-edge distances (the IPC toolkit's parallel cutoff: |ea x eb|^2 < 1e-20 max(1, |ea|^2 |eb|^2))
+__device__ __forceinline__ double ccd_distance(const CcdPair& P)
+{
+    int type;
+    if (!P.ee) return ::sqrt(point_triangle_sq_distance(type, P.x[0], P.x[1], P.x[2], P.x[3]));
+    const D3 u = P.x[1] - P.x[0], v = P.x[3] - P.x[2];
+    const double uv = sq3(u) * sq3(v);
+    if (sq3(cross3(u, v)) < 1e-20 * (uv > 1.0 ? uv : 1.0)) {
+        const double a = fmin(point_segment_sq(P.x[0], P.x[2], P.x[3]), point_segment_sq(P.x[1], P.x[2], P.x[3]));
+        const double b = fmin(point_segment_sq(P.x[2], P.x[0], P.x[1]), point_segment_sq(P.x[3], P.x[0], P.x[1]));
+        return ::sqrt(fmin(a, b));
+    }
+    return ::sqrt(edge_edge_sq_distance(type, P.x[0], P.x[1], P.x[2], P.x[3]));
+}
+// One lane per candidate: pairs that touch at the start (d = 0: the intersection test's business) are counted and skipped; a pair with
+// l_p <= eta d(0) cannot close eta of its gap within t <= 1 and is dropped. The rest is compacted (ballot + one atomic per wavefront) so that
+// the iterative kernel runs on pairs that all iterate. Also sets the time of impact to 1.
+__global__ __launch_bounds__(CB) void k_ccd_filter(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, double eta, const uint64_t* __restrict__ keys,
+                                                  int key_cap, int* __restrict__ counters, uint64_t* __restrict__ surv)
+{
+    const int i = blockIdx.x * CB + threadIdx.x, lane = threadIdx.x & 63;
+    const int n = min(counters[0], key_cap);
+    if (i == 0) *reinterpret_cast<unsigned long long*>(counters + CCD_TOI) = (unsigned long long)__double_as_longlong(1.0);
+    if ((i & ~63) >= n) return;  // (wave-uniform)
+    bool keep = false, touching = false;
+    uint64_t key = 0;
+    if (i < n) {
+        key = keys[i];
+        const CcdPair P = ccd_pair(d, key, xa, xb);
+        const double d0 = ccd_distance(P);
+        touching = !(d0 > 0.0);
+        keep = !touching && ccd_lp(P) > eta * d0;
+    }
+    const unsigned long long mk = __ballot(keep), mt = __ballot(touching);
+    int base = 0;
+    if (lane == 0 && mk) base = atomicAdd(&counters[CCD_N_SURV], __popcll(mk));
+    base = __shfl(base, 0, 64);
+    if (keep) surv[base + __popcll(mk & ((1ull << lane) - 1ull))] = key;
+    if (lane == 0 && mt) atomicAdd(&counters[CCD_N_SKIPPED], __popcll(mt));
+}
+// Additive CCD of the filter's survivors. t_c is the running minimum over all pairs (a relaxed read of the device scalar): a pair that passes
+// it cannot lower the minimum and stops. Each pair's sequence of advances does not depend on t_c, only where it stops, so the minimum is
+// the same whatever order the pairs finish in. Result: one 64-bit atomic min per wavefront on the bits of a non-negative double.
+__global__ __launch_bounds__(CB) void k_ccd_accd(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, double eta, const uint64_t* __restrict__ surv,
+                                                int* __restrict__ counters)
+{
+    unsigned long long* toi_bits = reinterpret_cast<unsigned long long*>(counters + CCD_TOI);
+    const int n = counters[CCD_N_SURV];
+    double best = 1.0;
+    int capped = 0;
+    for (int i = blockIdx.x * CB + threadIdx.x; i < n; i += gridDim.x * CB) {
+        CcdPair P = ccd_pair(d, surv[i], xa, xb);
+        const double lp = ccd_lp(P);
+        double dist = ccd_distance(P);
+        const double gap = (1.0 - eta) * dist;
+        double t = 0.0;
+        for (int it = 0;;) {
+            const double tc = __longlong_as_double((long long)__hip_atomic_load(toi_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            const double step = eta * dist / lp;
+#pragma unroll
+            for (int k = 0; k < 4; k++) P.x[k] = P.x[k] + step * P.dx[k];
+            dist = ccd_distance(P);
+            if (t > 0.0 && dist < gap) {  // hit: t is the last position known to keep (1 - eta) of the gap
+                best = t < best ? t : best;
+                break;
+            }
+            t += step;
+            if (t > tc) break;  // (no hit before the current minimum)
+            if (++it == CCD_MAX_ITERATIONS) {  // still a lower bound
+                best = t < best ? t : best;
+                capped++;
+                break;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double other = __shfl_xor(best, o, 64);
+        best = other < best ? other : best;
+        capped += __shfl_xor(capped, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (best < 1.0) atomicMin(toi_bits, (unsigned long long)__double_as_longlong(best));
+        if (capped) atomicAdd(&counters[CCD_N_CAPPED], capped);
+    }
+}
 }  // namespace
 
 // ======================================================================================================================================
-struct ContactSystem
+// sweep and prune: the sorted, banded box list of one search (the barrier / intersection searches share one; the CCD query has its own)
+struct BoxSweep
+{
+    DevBuf<uint64_t> bp_keys, bp_keys_alt;
+    DevBuf<uint32_t> bp_idx, bp_idx_alt;
+    DevBuf<float> s_aabb, s_lo;
+    DevBuf<uint32_t> bp_cnt, bp_off;
+    DevBuf<int> seg;
+    const uint32_t* s_idx = nullptr;
+    Bands bands{-1, -1, 0.f, 1.f, 0.f};
+    int bp_cap = 0;
+    int64_t n_updates = 0;
+    DevBuf<int> sweep_tasks;  // (entry, first candidate, end) of the split-off parts of long sweep ranges + their count
+};
+struct ContactSystem : BoxSweep
 {
     mistark_contact_arrays arr{};
     struct Mesh
@@ -1015,16 +1241,6 @@ struct ContactSystem
     DevBuf<double> mu, X;
     DevBuf<float> aabb;
     DevBuf<uint64_t> keys, keys_alt, prev;
-    // sweep and prune
-    DevBuf<uint64_t> bp_keys, bp_keys_alt;
-    DevBuf<uint32_t> bp_idx, bp_idx_alt;
-    DevBuf<float> s_aabb, s_lo;
-    DevBuf<uint32_t> bp_cnt, bp_off;
-    DevBuf<int> seg;
-    const uint32_t* s_idx = nullptr;
-    Bands bands{-1, -1, 0.f, 1.f, 0.f};
-    int bp_cap = 0;
-    int64_t n_updates = 0;
     bool brute_force = false;  // ablation / fallback: LDS-tiled all-pairs kernels
     int64_t n_prev = -1;  // keys of the barrier tables currently installed (-1: none)
     DevBuf<int> counters;  // [0] candidates, [1] intersections, [2] differs, [8..8+N_TABLES] bounds, [48..51] box list (k_bp_fill; [51] = entries needed)
@@ -1045,7 +1261,14 @@ struct ContactSystem
     double cache_dt = 0.0;
     int64_t cache_n = 0;
     DevBuf<double> thick_override;  // standalone detector (mistark_cd_*): no thickness filter, one huge value per mesh
-    DevBuf<int> sweep_tasks;  // (entry, first candidate, end) of the split-off parts of long sweep ranges + their count
+    // continuous collision detection (ccd_query): start / end positions, swept boxes, box list, candidate pairs, survivors of the filter, counters
+    DevBuf<double> ccd_xa, ccd_xb;
+    DevBuf<float> ccd_aabb;
+    BoxSweep ccd_sweep;
+    DevBuf<uint64_t> ccd_keys, ccd_surv;
+    DevBuf<int> ccd_counters;
+    size_t ccd_key_cap = 0;
+    int64_t n_ccd_queries = 0, n_ccd_skipped = 0, n_ccd_capped = 0;
     DevBuf<uint8_t> cub_tmp;
     DevBuf<TableDev> tables_dev;
     size_t key_cap = 0;
@@ -1064,6 +1287,11 @@ struct ContactSystem
 // sets, shared anyway). Every rank keeps them as ghosts (shard.hip).
 int64_t contact_sharded_searches(const Context& c) { return c.contact ? c.contact->n_sharded_searches : 0; }
 int64_t contact_searches(const Context& c, bool repeated) { return !c.contact ? 0 : (repeated ? c.contact->n_repeated_searches : c.contact->n_searches); }
+int64_t contact_ccd_counter(const Context& c, int which)
+{
+    if (!c.contact) return 0;
+    return which == 0 ? c.contact->n_ccd_queries : (which == 1 ? c.contact->n_ccd_skipped : c.contact->n_ccd_capped);
+}
 void contact_shared_rows(Context& c, std::vector<int32_t>& rows)
 {
     if (!c.contact) return;
@@ -1257,7 +1485,7 @@ void update_vertices(Context& c, ContactSystem& cs, const ContactDev& d, double 
     const int np = cs.n_v + cs.n_t + cs.n_e;
     hipLaunchKernelGGL(k_contact_aabbs, dim3((np + CB - 1) / CB), dim3(CB), 0, c.stream, d, enl, cs.aabb.p);
 }
-void choose_axes(Context& c, ContactSystem& cs)
+void choose_axes(Context& c, ContactSystem& cs, BoxSweep& sw, const double* X_dev)
 {
     // sweep axis = the axis along which the collision vertices are spread widest, band axis = the second; re-evaluated now and then (a stale
     // choice only costs speed: band indices are clamped, monotone functions of the coordinate). "Spread" is the VARIANCE of the vertices, not the
@@ -1265,9 +1493,9 @@ void choose_axes(Context& c, ContactSystem& cs)
     // while 66 k of its 66 k + 8 vertices lie within 5 cm of one z; swept along z every cloth primitive met a thousand candidates per band
     // (2.3-2.8 ms per sweep, 74 % of that scene's kernel time; along x: what the flat floor box of round 4's configs[2] took, 0.3-0.4 ms).
     // The bands still cover the whole extent of their axis.
-    if (cs.bands.axis >= 0 && (cs.n_updates % 256) != 0) return;
+    if (sw.bands.axis >= 0 && (sw.n_updates % 256) != 0) return;
     std::vector<double> X(3 * (size_t)cs.n_v);
-    MS_CHECK(hipMemcpyAsync(X.data(), cs.X.p, X.size() * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    MS_CHECK(hipMemcpyAsync(X.data(), X_dev, X.size() * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     MS_CHECK(hipStreamSynchronize(c.stream));
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, sum[3] = {0, 0, 0}, sq[3] = {0, 0, 0};
     for (int i = 0; i < cs.n_v; i++)
@@ -1286,37 +1514,38 @@ void choose_axes(Context& c, ContactSystem& cs)
     }
     int order[3] = {0, 1, 2};
     std::stable_sort(order, order + 3, [&](int a, int b) { return var[a] > var[b]; });
-    cs.bands.axis = order[0];
-    cs.bands.band_axis = order[1];
+    sw.bands.axis = order[0];
+    sw.bands.band_axis = order[1];
     const double ext = std::max(hi[order[1]] - lo[order[1]], 1e-12);
-    cs.bands.band_lo = (float)lo[order[1]];
-    cs.bands.band_scale = (float)(NBANDS / ext);
+    sw.bands.band_lo = (float)lo[order[1]];
+    sw.bands.band_scale = (float)(NBANDS / ext);
 }
 // false: the entry list did not fit (capacity grown, caller repeats)
-void sort_boxes(Context& c, ContactSystem& cs, const ContactDev& d)
+void sort_boxes(Context& c, ContactSystem& cs, BoxSweep& sw, const ContactDev& d, const double* X_dev, int* counters)
 {
-    choose_axes(c, cs);
-    cs.n_updates++;
+    choose_axes(c, cs, sw, X_dev);
+    sw.n_updates++;
     const int n = cs.n_v + cs.n_t + cs.n_e;
-    if (cs.bp_cap < n + n / 2 + 4096) cs.bp_cap = n + n / 2 + 4096;
-    const int cap = cs.bp_cap;
-    cs.bp_cnt.ensure((size_t)n + 1); cs.bp_off.ensure((size_t)n + 1);
-    cs.bp_keys.ensure(cap); cs.bp_keys_alt.ensure(cap); cs.bp_idx.ensure(cap); cs.bp_idx_alt.ensure(cap);
-    cs.s_aabb.ensure(6 * (size_t)cap); cs.s_lo.ensure(cap); cs.seg.ensure(3 * NBANDS + 2);
-    hipLaunchKernelGGL(k_bp_count, dim3((n + 1 + CB - 1) / CB), dim3(CB), 0, c.stream, d, cs.bands, cs.bp_cnt.p);
+    if (sw.bp_cap < n + n / 2 + 4096) sw.bp_cap = n + n / 2 + 4096;
+    const int cap = sw.bp_cap;
+    sw.bp_cnt.ensure((size_t)n + 1); sw.bp_off.ensure((size_t)n + 1);
+    sw.bp_keys.ensure(cap); sw.bp_keys_alt.ensure(cap); sw.bp_idx.ensure(cap); sw.bp_idx_alt.ensure(cap);
+    sw.s_aabb.ensure(6 * (size_t)cap); sw.s_lo.ensure(cap); sw.seg.ensure(3 * NBANDS + 2);
+    hipLaunchKernelGGL(k_bp_count, dim3((n + 1 + CB - 1) / CB), dim3(CB), 0, c.stream, d, sw.bands, sw.bp_cnt.p);
     size_t tmp = 0;
-    MS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cs.bp_cnt.p, cs.bp_off.p, n + 1, c.stream));
+    MS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, sw.bp_cnt.p, sw.bp_off.p, n + 1, c.stream));
     cs.cub_tmp.ensure(tmp);
-    MS_CHECK(hipcub::DeviceScan::ExclusiveSum(cs.cub_tmp.p, tmp, cs.bp_cnt.p, cs.bp_off.p, n + 1, c.stream));
-    hipLaunchKernelGGL(k_bp_fill, dim3((n + CB - 1) / CB), dim3(CB), 0, c.stream, d, cs.bands, (const uint32_t*)cs.bp_off.p, cs.bp_keys.p, cs.bp_idx.p, cap, cs.counters.p + 48);
-    hipcub::DoubleBuffer<uint64_t> dk(cs.bp_keys.p, cs.bp_keys_alt.p);
-    hipcub::DoubleBuffer<uint32_t> dv(cs.bp_idx.p, cs.bp_idx_alt.p);
+    MS_CHECK(hipcub::DeviceScan::ExclusiveSum(cs.cub_tmp.p, tmp, sw.bp_cnt.p, sw.bp_off.p, n + 1, c.stream));
+    hipLaunchKernelGGL(k_bp_fill, dim3((n + CB - 1) / CB), dim3(CB), 0, c.stream, d, sw.bands, (const uint32_t*)sw.bp_off.p, sw.bp_keys.p, sw.bp_idx.p, cap, counters + 48);
+    hipcub::DoubleBuffer<uint64_t> dk(sw.bp_keys.p, sw.bp_keys_alt.p);
+    hipcub::DoubleBuffer<uint32_t> dv(sw.bp_idx.p, sw.bp_idx_alt.p);
     MS_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, dk, dv, cap, 0, 32 + BAND_KEY_BITS, c.stream));
     cs.cub_tmp.ensure(tmp);
     MS_CHECK(hipcub::DeviceRadixSort::SortPairs(cs.cub_tmp.p, tmp, dk, dv, cap, 0, 32 + BAND_KEY_BITS, c.stream));
-    cs.s_idx = dv.Current();
-    hipLaunchKernelGGL(k_bp_gather, dim3((cap + 1 + CB - 1) / CB), dim3(CB), 0, c.stream, d, cs.bands, (const uint64_t*)dk.Current(), cs.s_idx, cap, cs.s_aabb.p, cs.s_lo.p, cs.seg.p);
+    sw.s_idx = dv.Current();
+    hipLaunchKernelGGL(k_bp_gather, dim3((cap + 1 + CB - 1) / CB), dim3(CB), 0, c.stream, d, sw.bands, (const uint64_t*)dk.Current(), sw.s_idx, cap, sw.s_aabb.p, sw.s_lo.p, sw.seg.p);
 }
+void sort_boxes(Context& c, ContactSystem& cs, const ContactDev& d) { sort_boxes(c, cs, cs, d, cs.X.p, cs.counters.p); }
 // first capacity of the contact key list (it grows on demand; MISTARK_CONTACT_KEY_CAP: a small value makes the tests walk the growth path)
 size_t initial_key_cap()
 {
@@ -1393,19 +1622,23 @@ bool sharded_search_overflowed(Context& c, ContactSystem& cs, const int* h)
     return true;
 }
 template <bool PROX, bool FR>
+void launch_sweep(Context& c, ContactSystem& cs, BoxSweep& sw, const ContactDev& d, double enl2, uint64_t* keys, int* counters, size_t key_cap, bool sharded)
+{
+    sw.sweep_tasks.ensure(3 * (size_t)SWEEP_TASK_CAP + 4);
+    // (the task counter lives among the search's counters, which every caller zeroes before the search: counters[56])
+    int* task_count = counters + 56;
+    const int pt_on = (int)(cs.pt_enabled && cs.n_t > 0), ee_on = (int)(cs.ee_enabled && cs.n_e > 1);
+    const int W = sharded ? c.world : 1, me = sharded ? c.rank : 0;
+    const int wgs = (sw.bp_cap + CB / SWEEP_SUB - 1) / (CB / SWEEP_SUB);
+    hipLaunchKernelGGL((k_sweep<PROX, FR>), dim3((wgs + W - 1) / W), dim3(CB), 0, c.stream, d, sw.bands, sw.s_idx, (const float*)sw.s_aabb.p, (const float*)sw.s_lo.p,
+                       (const int*)sw.seg.p, pt_on, ee_on, enl2, keys, counters, (int)key_cap, task_count, sw.sweep_tasks.p, me, W);
+    hipLaunchKernelGGL((k_sweep_tasks<PROX, FR>), dim3(SWEEP_TASK_WAVES / (CB / 64)), dim3(CB), 0, c.stream, d, sw.bands, sw.s_idx, (const float*)sw.s_aabb.p, (const int*)sw.seg.p, pt_on,
+                       ee_on, enl2, keys, counters, (int)key_cap, (const int*)task_count, (const int*)sw.sweep_tasks.p);
+}
+template <bool PROX, bool FR>
 void launch_sweep(Context& c, ContactSystem& cs, const ContactDev& d, double enl2)
 {
-    cs.sweep_tasks.ensure(3 * (size_t)SWEEP_TASK_CAP + 4);
-    // (the task counter lives among the search's counters, which every caller zeroes before the search: counters[56])
-    int* task_count = cs.counters.p + 56;
-    const int pt_on = (int)(cs.pt_enabled && cs.n_t > 0), ee_on = (int)(cs.ee_enabled && cs.n_e > 1);
-    const bool sharded = search_is_sharded(c, cs);
-    const int W = sharded ? c.world : 1, me = sharded ? c.rank : 0;
-    const int wgs = (cs.bp_cap + CB / SWEEP_SUB - 1) / (CB / SWEEP_SUB);
-    hipLaunchKernelGGL((k_sweep<PROX, FR>), dim3((wgs + W - 1) / W), dim3(CB), 0, c.stream, d, cs.bands, cs.s_idx, (const float*)cs.s_aabb.p, (const float*)cs.s_lo.p,
-                       (const int*)cs.seg.p, pt_on, ee_on, enl2, cs.keys.p, cs.counters.p, (int)cs.key_cap, task_count, cs.sweep_tasks.p, me, W);
-    hipLaunchKernelGGL((k_sweep_tasks<PROX, FR>), dim3(SWEEP_TASK_WAVES / (CB / 64)), dim3(CB), 0, c.stream, d, cs.bands, cs.s_idx, (const float*)cs.s_aabb.p, (const int*)cs.seg.p, pt_on,
-                       ee_on, enl2, cs.keys.p, cs.counters.p, (int)cs.key_cap, (const int*)task_count, (const int*)cs.sweep_tasks.p);
+    launch_sweep<PROX, FR>(c, cs, cs, d, enl2, cs.keys.p, cs.counters.p, cs.key_cap, search_is_sharded(c, cs));
 }
 // padded length of the key sort for the next search
 int padded_key_count(const ContactSystem& cs)
@@ -1676,6 +1909,83 @@ int64_t count_intersections_uncached(Context& c, double dt)
     fetch(c, h, cs.counters.p, sizeof(h));
     return h[1];
 }
+// ---- continuous collision detection -------------------------------------------------------------------------------------------------
+struct CcdResult
+{
+    double toi = 1.0;
+    int64_t n_candidates = 0;
+};
+// Largest fraction of the straight-line motion cs.ccd_xa -> cs.ccd_xb that keeps every candidate pair's distance above (1 - eta) of its start
+// value. Reads and writes only the CCD buffers: the installed tables, the barrier search's key lists, box list and caches are left as they are.
+CcdResult ccd_query(Context& c, ContactSystem& cs, ContactDev d, double eta)
+{
+    const int np = cs.n_v + cs.n_t + cs.n_e;
+    cs.ccd_aabb.ensure(6 * (size_t)np);
+    hipLaunchKernelGGL(k_ccd_aabbs, dim3((np + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, cs.ccd_aabb.p);
+    d.aabb = cs.ccd_aabb.p;
+    d.X = cs.ccd_xa.p;
+    d.broad_only = 0;
+    d.ccd = 1;
+    if (cs.ccd_key_cap == 0) cs.ccd_key_cap = initial_key_cap();
+    cs.ccd_counters.ensure(64);
+    int h[64];
+    for (;;) {
+        cs.ccd_keys.ensure(cs.ccd_key_cap);
+        cs.ccd_surv.ensure(cs.ccd_key_cap);
+        const int cap = (int)cs.ccd_key_cap;
+        fill_async(c.stream, cs.ccd_counters.p, 0, 64 * sizeof(int));
+        sort_boxes(c, cs, cs.ccd_sweep, d, cs.ccd_xa.p, cs.ccd_counters.p);
+        launch_sweep<true, false>(c, cs, cs.ccd_sweep, d, 0.0, cs.ccd_keys.p, cs.ccd_counters.p, cs.ccd_key_cap, false);
+        // (both kernels take their lengths from the device: one read-back per query)
+        hipLaunchKernelGGL(k_ccd_filter, dim3((cap + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, eta,
+                           (const uint64_t*)cs.ccd_keys.p, cap, cs.ccd_counters.p, cs.ccd_surv.p);
+        hipLaunchKernelGGL(k_ccd_accd, dim3(std::min((cap + CB - 1) / CB, 2048)), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, eta,
+                           (const uint64_t*)cs.ccd_surv.p, cs.ccd_counters.p);
+        fetch(c, h, cs.ccd_counters.p, sizeof(h));
+        if (h[51] > cs.ccd_sweep.bp_cap) {  // the banded box list did not fit: grow and query again
+            cs.ccd_sweep.bp_cap = h[51] + h[51] / 4;
+            continue;
+        }
+        if ((size_t)h[0] > cs.ccd_key_cap) {  // the candidate list did not fit
+            cs.ccd_key_cap = (size_t)h[0] + h[0] / 2;
+            continue;
+        }
+        break;
+    }
+    CcdResult r;
+    std::memcpy(&r.toi, h + CCD_TOI, sizeof(double));
+    r.n_candidates = h[0];
+    cs.n_ccd_queries++;
+    cs.n_ccd_skipped += h[CCD_N_SKIPPED];
+    cs.n_ccd_capped += h[CCD_N_CAPPED];
+    return r;
+}
+// the Newton direction's counterpart of a DoF-view array (nullptr: the array does not move along du)
+const double* du_view(Context& c, int id)
+{
+    if (id < 0) return nullptr;
+    const Array& a = c.arrays[(size_t)id];
+    if (a.dof_set < 0) return nullptr;
+    const DofSet& s = c.dof_sets[(size_t)a.dof_set];
+    return c.du.p && c.du.cap >= (size_t)(s.offset + s.n) ? c.du.p + s.offset : nullptr;
+}
+// collision vertices at u (the line search's start) and u + du (the engine's current DoFs and Newton direction)
+CcdResult contact_max_step(Context& c, double dt, double eta)
+{
+    ContactSystem& cs = CS(c);
+    if (c.world > 1) throw Error("contact: mistark_contact_max_step is not available on a sharded context");
+    if (!(eta > 0.0 && eta <= 1.0)) throw Error("contact: conservative_rescaling must lie in (0, 1]");
+    if (cs.meshes.empty()) return CcdResult{};
+    prepare(c);
+    upload_meshes(c, cs);
+    const ContactDev d = dev_view(c, cs);
+    cs.ccd_xa.ensure(3 * (size_t)cs.n_v);
+    cs.ccd_xb.ensure(3 * (size_t)cs.n_v);
+    hipLaunchKernelGGL(k_ccd_vertices, dim3((cs.n_v + CB - 1) / CB), dim3(CB), 0, c.stream, d, arr_dev(c, cs.arr.x0), arr_dev(c, cs.arr.v1), du_view(c, cs.arr.v1),
+                       arr_dev(c, cs.arr.rb_xloc), arr_dev(c, cs.arr.rb_v1), du_view(c, cs.arr.rb_v1), arr_dev(c, cs.arr.rb_w1), du_view(c, cs.arr.rb_w1),
+                       arr_dev(c, cs.arr.rb_t0), arr_dev(c, cs.arr.rb_q0), dt, cs.ccd_xa.p, cs.ccd_xb.p);
+    return ccd_query(c, cs, d, eta);
+}
 int find_table(const char* name)
 {
     for (int t = 0; t < N_TABLES; t++)
@@ -1726,7 +2036,7 @@ struct StandaloneDetector
 {
     Context c;
     std::vector<const double*> xm;
-    PinnedBuf<double> X;
+    PinnedBuf<double> X, X1;  // (X1: end positions of mistark_cd_run_ccd)
     std::vector<int32_t> rows[6], et_rows, bp_rows[2];  // (bp_rows: the last broad-phase listing, point-triangle | edge-edge, 4 columns)
     std::vector<double> dist[6];
     PinnedBuf<uint64_t> keys;
@@ -2143,6 +2453,33 @@ int mistark_cd_run_intersection(mistark_cd* cd, int32_t* n_pairs)
     D.et_valid = true;
     CD_END(0)
 }
+int mistark_cd_run_ccd(mistark_cd* cd, const double* const* x1, double conservative_rescaling, double* toi, int32_t* n_candidates)
+{
+    CD_BEGIN
+    StandaloneDetector& D = cd->D;
+    Context& c = D.c;
+    ContactSystem& cs = CS(c);
+    MS_CHECK(hipSetDevice(c.device));
+    if (toi) *toi = 1.0;
+    if (n_candidates) *n_candidates = 0;
+    if (!(conservative_rescaling > 0.0 && conservative_rescaling <= 1.0)) throw Error("cd: conservative_rescaling must lie in (0, 1]");
+    if (cs.meshes.empty()) return 0;
+    if (!x1) throw Error("cd: null end positions");
+    for (size_t g = 0; g < cs.meshes.size(); g++)
+        if (!x1[g]) throw Error("cd: null end positions of mesh " + std::to_string(g));
+    if (cs.meshes_dirty) upload_meshes(c, cs);
+    cd_gather_positions(D);
+    D.X1.resize(D.X.size());
+    for (size_t g = 0; g < cs.meshes.size(); g++) std::memcpy(D.X1.data() + 3 * (size_t)cs.meshes[g].v_off, x1[g], 3 * (size_t)cs.meshes[g].n_v * sizeof(double));
+    cs.ccd_xa.ensure(D.X.size());
+    cs.ccd_xb.ensure(D.X.size());
+    MS_CHECK(hipMemcpyAsync(cs.ccd_xa.p, D.X.data(), D.X.size() * sizeof(double), hipMemcpyHostToDevice, c.stream));
+    MS_CHECK(hipMemcpyAsync(cs.ccd_xb.p, D.X1.data(), D.X1.size() * sizeof(double), hipMemcpyHostToDevice, c.stream));
+    const CcdResult r = ccd_query(c, cs, cd_view(D), conservative_rescaling);  // (its read-back waits for the uploads)
+    if (toi) *toi = r.toi;
+    if (n_candidates) *n_candidates = (int32_t)r.n_candidates;
+    CD_END(0)
+}
 int mistark_cd_get_intersections(mistark_cd* cd, int32_t* rows)
 {
     CD_BEGIN
@@ -2247,6 +2584,14 @@ int mistark_contact_count_intersections(mistark_ctx* ctx, double dt, int64_t* n_
     CAPI_BEGIN
     const int64_t n = count_intersections(ctx->c, dt);
     if (n_found) *n_found = n;
+    CAPI_END(0)
+}
+int mistark_contact_max_step(mistark_ctx* ctx, double dt, double conservative_rescaling, double* max_step, int64_t* n_candidates)
+{
+    CAPI_BEGIN
+    const CcdResult r = contact_max_step(ctx->c, dt, conservative_rescaling);
+    if (max_step) *max_step = r.toi;
+    if (n_candidates) *n_candidates = r.n_candidates;
     CAPI_END(0)
 }
 int mistark_contact_get_table(mistark_ctx* ctx, const char* potential, int32_t* conn, int32_t* n_rows, int32_t* stride)

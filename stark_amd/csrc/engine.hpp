@@ -572,6 +572,7 @@ void static_graph_order(Context& c, std::vector<int32_t>& rows_in_order);  // sh
 void ensure_pattern(Context& c);
 void contact_destroy(struct ContactSystem* cs);
 int64_t contact_searches(const Context& c, bool repeated);  // counters "contact_searches" / "contact_repeated_searches"
+int64_t contact_ccd_counter(const Context& c, int which);   // counters "ccd_queries" (0) / "ccd_skipped_pairs" (1) / "ccd_capped_pairs" (2)
 int64_t contact_sharded_searches(const Context& c);  // searches of a sharded problem whose sweep was dealt out to the ranks (contact.hip)
 void contact_shared_rows(Context& c, std::vector<int32_t>& rows);  // contact.hip
 int register_potential(Context& c, const char* name, const int32_t* conn, int32_t n_elem, int32_t conn_stride, const mistark_binding* bindings, int32_t n_bindings);

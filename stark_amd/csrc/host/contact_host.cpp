@@ -2,6 +2,7 @@
 // parameters, collision mesh bookkeeping, adaptive contact stiffness and the solver callbacks. Proximity / intersection
 // detection and the contact and friction tables live on the device (include/mistark_contact.h).
 #include <algorithm>
+#include <chrono>
 #include <stdexcept>
 
 #include "sim.hpp"
@@ -188,6 +189,33 @@ void EnergyFrictionalContact::_on_time_step_accepted()
 {
     contact_stiffness = std::max(global_params.min_contact_stiffness, 0.99 * contact_stiffness);  // :807-810
     _sync_stiffness();
+}
+void EnergyFrictionalContact::set_ccd(const CCDParams& p)
+{
+    if (p.enabled && !(p.conservative_rescaling > 0.0 && p.conservative_rescaling <= 1.0))
+        throw std::runtime_error("EnergyFrictionalContact::set_ccd: conservative_rescaling must lie in (0, 1]");
+    ccd = p;
+    auto& cbs = stark.callbacks->newton->max_allowed_step;
+    if (p.enabled && ccd_callback < 0) {
+        ccd_callback = (int)cbs.size();
+        cbs.push_back([this]() { return _max_allowed_step(); });
+    } else if (!p.enabled && ccd_callback >= 0) {
+        cbs.erase(cbs.begin() + ccd_callback);
+        ccd_callback = -1;
+    }
+}
+double EnergyFrictionalContact::_max_allowed_step()
+{
+    if (!is_initialized || !global_params.collisions_enabled || is_empty()) return 1.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    double t = 1.0;
+    int64_t n = 0;
+    stark.check(mistark_contact_max_step(stark.ctx, stark.dt, ccd.conservative_rescaling, &t, &n));
+    ccd_info.queries++;
+    if (t < 1.0) ccd_info.limited++;
+    ccd_info.last_candidates = n;
+    ccd_info.time += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return t;
 }
 bool EnergyFrictionalContact::_should_continue_execution()
 {

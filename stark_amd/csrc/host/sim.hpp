@@ -569,6 +569,18 @@ public:
     {
         double contact_thickness = 0.0;
     };
+    // continuous collision detection (not in the reference): every line search is bounded so that no collision pair closes more than
+    // conservative_rescaling of its gap along the step (mistark_contact_max_step)
+    struct CCDParams
+    {
+        bool enabled = false;
+        double conservative_rescaling = 0.9;
+    };
+    struct CCDInfo
+    {
+        int64_t queries = 0, limited = 0, last_candidates = 0;
+        double time = 0.0;  // seconds in the queries
+    };
     struct Handler
     {
         EnergyFrictionalContact* model = nullptr;
@@ -594,6 +606,10 @@ public:
     bool is_active() const { return is_initialized; }
     int64_t last_n_contacts = 0, last_n_friction_contacts = 0, n_detections = 0;
     void register_potentials(mistark_ctx* ctx) override;
+    // off: no max_allowed_step callback at all (the line search is what it is without CCD); on: one callback
+    void set_ccd(const CCDParams& p);
+    CCDParams get_ccd() const { return ccd; }
+    CCDInfo ccd_info;
 
 private:
     struct Mesh
@@ -616,7 +632,10 @@ private:
     std::vector<std::array<int, 2>> disabled_pairs;
     int id_k = -1;
     double k_uploaded = -1.0;
+    CCDParams ccd;
+    int ccd_callback = -1;  // index of the CCD callback in callbacks->newton->max_allowed_step
     double _init_contact_thickness(double t) const;
+    double _max_allowed_step();
     void _sync_stiffness();
     void _before_time_step();
     void _before_energy_evaluation();

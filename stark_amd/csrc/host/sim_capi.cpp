@@ -659,6 +659,30 @@ int mistark_sim_get_contact_info(mistark_sim* s, double* k, int64_t* n_contacts,
     if (n_detections) *n_detections = c.n_detections;
     SIM_END
 }
+int mistark_sim_set_contact_ccd(mistark_sim* s, int enabled, double conservative_rescaling)
+{
+    SIM_BEGIN
+    s->sim->interactions->contact->set_ccd(EnergyFrictionalContact::CCDParams{enabled != 0, conservative_rescaling});
+    SIM_END
+}
+int mistark_sim_get_ccd_info(mistark_sim* s, int64_t* n_queries, int64_t* n_limited, int64_t* last_candidates, int64_t* n_skipped, int64_t* n_capped, double* seconds)
+{
+    SIM_BEGIN
+    const EnergyFrictionalContact::CCDInfo& i = s->sim->interactions->contact->ccd_info;
+    if (n_queries) *n_queries = i.queries;
+    if (n_limited) *n_limited = i.limited;
+    if (last_candidates) *last_candidates = i.last_candidates;
+    if (seconds) *seconds = i.time;
+    int64_t skipped = 0, capped = 0;
+    mistark_ctx* ctx = s->sim->get_stark().ctx;
+    if (ctx && i.queries > 0) {
+        if (mistark_get_counter(ctx, "ccd_skipped_pairs", &skipped) != 0 || mistark_get_counter(ctx, "ccd_capped_pairs", &capped) != 0)
+            throw std::runtime_error(mistark_last_error(ctx));
+    }
+    if (n_skipped) *n_skipped = skipped;
+    if (n_capped) *n_capped = capped;
+    SIM_END
+}
 int mistark_sim_set_dist_rccl(mistark_sim* s, int rank, int world, const char unique_id[128])
 {
     SIM_BEGIN

@@ -170,6 +170,12 @@ class Engine:
         self._ck(self.L.mistark_contact_count_intersections(self.h, dt, C.byref(n)))
         return n.value
 
+    def contact_max_step(self, dt, conservative_rescaling=0.9):
+        """mistark_contact_max_step: (max_step, n_candidates) of the current Newton direction (inside a max_allowed_step callback)."""
+        t, n = C.c_double(), C.c_int64()
+        self._ck(self.L.mistark_contact_max_step(self.h, dt, conservative_rescaling, C.byref(t), C.byref(n)))
+        return t.value, n.value
+
     def contact_table(self, name: str) -> np.ndarray:
         n, st = C.c_int32(), C.c_int32()
         self._ck(self.L.mistark_contact_get_table(self.h, name.encode(), None, C.byref(n), C.byref(st)))

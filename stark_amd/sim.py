@@ -128,6 +128,9 @@ def _lib():
         L.mistark_sim_set_dist_local.argtypes = [p, p, C.c_int, C.c_int]
         L.mistark_sim_set_dist_ipc.argtypes = [p, p, C.c_int, C.c_int]
         L.mistark_sim_get_contact_info.argtypes = [p, D, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mistark_sim_set_contact_ccd.argtypes = [p, C.c_int, C.c_double]
+        I64 = C.POINTER(C.c_int64)
+        L.mistark_sim_get_ccd_info.argtypes = [p, I64, I64, I64, I64, I64, D]
         _bound = True
     return L
 
@@ -407,6 +410,17 @@ class Simulation:
         k, n, nf, nd = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
         self._ck(self.L.mistark_sim_get_contact_info(self.h, C.byref(k), C.byref(n), C.byref(nf), C.byref(nd)))
         return dict(contact_stiffness=k.value, n_contacts=n.value, n_friction_contacts=nf.value, n_detections=nd.value)
+
+    def set_contact_ccd(self, enabled=True, conservative_rescaling=0.9):
+        """Continuous collision detection: every line search is bounded so that no collision pair's distance falls below
+        (1 - conservative_rescaling) of its start value along the step. Off (the default) registers nothing."""
+        self._ck(self.L.mistark_sim_set_contact_ccd(self.h, 1 if enabled else 0, float(conservative_rescaling)))
+
+    def ccd_info(self):
+        q, lim, cand, sk, cap = (C.c_int64() for _ in range(5))
+        t = C.c_double()
+        self._ck(self.L.mistark_sim_get_ccd_info(self.h, C.byref(q), C.byref(lim), C.byref(cand), C.byref(sk), C.byref(cap), C.byref(t)))
+        return dict(queries=q.value, limited=lim.value, last_candidates=cand.value, skipped_pairs=sk.value, capped_pairs=cap.value, seconds=t.value)
 
     def prescribe_inside_aabb(self, point_set, center, dim, stiffness, tolerance=0.0) -> int:
         return self._ck(self.L.mistark_sim_prescribe_inside_aabb(self.h, point_set, _d3(center), _d3(dim), stiffness, tolerance))
