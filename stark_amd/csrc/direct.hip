@@ -399,6 +399,10 @@ bool direct_llt_blocktri(Context& c, const double* rhs_dev, double* x_dev)
     if (gb > cap)
         throw Error("DirectLLT: the band of this system (" + std::to_string(n) + " unknowns, half bandwidth " + std::to_string(m) + ") needs " + std::to_string((int)gb) +
                     " GB as dense blocks (limit MISTARK_DIRECT_MAX_GB = " + std::to_string((int)cap) + "); use the block-Jacobi PCG");
+    c.llt_last_path = 1;
+    c.llt_last_panel_rows = mb;
+    c.llt_last_panels = N;
+    c.llt_last_fronts = 0;
     const int64_t ld = 2 * m;
     const size_t panel = (size_t)ld * (size_t)m;  // doubles per block column
     c.llt_D.ensure((size_t)N * panel);
@@ -1011,6 +1015,9 @@ bool direct_llt_multifrontal(Context& c, const double* rhs_dev, double* x_dev, d
     if (c.llt_mf_gb > cap_gb)
         throw Error("DirectLLT: the factor of this system (" + std::to_string(n) + " unknowns) needs " + std::to_string((int)c.llt_mf_gb) +
                     " GB (limit MISTARK_DIRECT_MAX_GB = " + std::to_string((int)cap_gb) + "); use the block-Jacobi PCG");
+    c.llt_last_path = 2;
+    c.llt_last_panel_rows = M.max_nf / 3;
+    c.llt_last_panels = c.llt_last_fronts = (int64_t)M.fronts.size();
     M.panels.ensure(std::max<size_t>(M.panel_doubles, 1));
     M.arena.ensure(std::max<size_t>(M.arena_doubles, 1));
     M.work.ensure((size_t)M.max_nf + 8);
@@ -1110,6 +1117,10 @@ static bool direct_llt_solver_numbering(Context& c, const double* rhs_dev, doubl
 {
     const int n = (int)c.ndofs;
     if (c.ndofs > MAX_DIRECT_DOFS) return direct_llt_blocktri(c, rhs_dev, x_dev);
+    c.llt_last_path = 0;
+    c.llt_last_panel_rows = c.nbr;
+    c.llt_last_panels = 1;
+    c.llt_last_fronts = 0;
     c.dense.ensure((size_t)n * n);
     c.counters.ensure(8);
     MS_CHECK(hipMemsetAsync(c.dense.p, 0, (size_t)n * n * sizeof(double), c.stream));

@@ -333,6 +333,10 @@ struct Context
     double llt_mf_gb = 0.0;
     bool llt_no_coords = false;  // multifrontal ordering by breadth-first level sets even when positions are known (cross-check)
     int llt_multifrontal = 0;  // 0: when the band costs more than 2 GB, 1: always beyond the dense limit, -1: never
+    // what the last DirectLLT solve ran (counters llt_path, llt_panel_rows, llt_panels, llt_fronts): path 0 dense, 1 band, 2 multifrontal, -1 none yet;
+    // block rows per panel (multifrontal: of the largest front), panels, fronts
+    int llt_last_path = -1;
+    int64_t llt_last_panel_rows = 0, llt_last_panels = 0, llt_last_fronts = 0;
     uint64_t pattern_version = 1, llt_pattern_version = 0;  // bumped by every pattern build
     bool have_matrix = false;
     bool matrix_current = false;    // the assembled matrix reflects the current element Hessians
