@@ -791,14 +791,14 @@ int mistark_spmv(mistark_ctx* ctx, const double* x_host, double* y_host)
     MS_CHECK(hipMemcpyAsync(c.tmp_a.p, x_host, (size_t)c.ndofs * sizeof(double), hipMemcpyHostToDevice, c.stream));
     if (c.world > 1) {  // this rank's rows of y from its rows of A, gathered into the whole vector on every rank
         shard_to_local(c, c.tmp_a.p, c.p.p, true);
-        spmv_device(c, c.p.p, c.q.p, nullptr, nullptr, true);
+        spmv_device(c, c.p.p, c.q.p, nullptr, nullptr);
         shard_gather_global(c, c.q.p, c.tmp_b.p);
     } else if (c.perm_active) {  // the matrix lives in solver numbering
         rows_to_solver(c, c.tmp_a.p, c.p.p);
-        spmv_device(c, c.p.p, c.q.p, nullptr, nullptr, true);
+        spmv_device(c, c.p.p, c.q.p, nullptr, nullptr);
         rows_from_solver(c, c.q.p, c.tmp_b.p);
     } else {
-        spmv_device(c, c.tmp_a.p, c.tmp_b.p, nullptr, nullptr, true);
+        spmv_device(c, c.tmp_a.p, c.tmp_b.p, nullptr, nullptr);
     }
     MS_CHECK(hipMemcpyAsync(y_host, c.tmp_b.p, (size_t)c.ndofs * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     MS_CHECK(hipStreamSynchronize(c.stream));

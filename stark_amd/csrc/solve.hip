@@ -94,13 +94,11 @@ __device__ __forceinline__ void sym3_inverse(const float* m, float* o)
     o[7] = -tmp5 * (m[0] * m[5] - m[1] * m[2]);
     o[5] = o[7];
 }
-__global__ __launch_bounds__(BLOCK) void k_block_diag_inverse(const float* __restrict__ vals, const int32_t* __restrict__ diag_slot, const float* __restrict__ vals_dyn,
-                                                              const int32_t* __restrict__ diag_slot_dyn, int64_t nbr, float* __restrict__ dinv)
+// the diagonal block of block row r: the static part's plus, where the contact part has one, the contact part's
+__device__ __forceinline__ void load_diag_block(const float* __restrict__ vals, const int32_t* __restrict__ diag_slot, const float* __restrict__ vals_dyn,
+                                                const int32_t* __restrict__ diag_slot_dyn, int64_t r, float* m)
 {
-    const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (r >= nbr) return;
     const uint32_t s = (uint32_t)diag_slot[r];
-    float m[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) m[k] = vals[tile_val_index(s, k)];
     if (vals_dyn) {
@@ -110,6 +108,14 @@ __global__ __launch_bounds__(BLOCK) void k_block_diag_inverse(const float* __res
             for (int k = 0; k < 9; k++) m[k] += vals_dyn[tile_val_index((uint32_t)sd, k)];
         }
     }
+}
+__global__ __launch_bounds__(BLOCK) void k_block_diag_inverse(const float* __restrict__ vals, const int32_t* __restrict__ diag_slot, const float* __restrict__ vals_dyn,
+                                                              const int32_t* __restrict__ diag_slot_dyn, int64_t nbr, float* __restrict__ dinv)
+{
+    const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= nbr) return;
+    float m[9];
+    load_diag_block(vals, diag_slot, vals_dyn, diag_slot_dyn, r, m);
     sym3_inverse(m, dinv + 9 * r);
 }
 
@@ -128,6 +134,29 @@ __device__ __forceinline__ double contrib(const double* __restrict__ elemH, cons
     const double vd = elemH[d ? (size_t)desc * 9 + (size_t)comp : (size_t)0];
     return f ? (double)vf : (d ? vd : 0.0);
 }
+// where block `slot` is stored (the static part keeps its blocks in tile order: store_slot), and the only-dirty test of project()'s partial
+// assembly (the flags are indexed like the values: by storage position)
+template <class I>
+__device__ __forceinline__ uint32_t stored_at(const uint32_t* __restrict__ store_slot, I slot)
+{
+    return store_slot ? store_slot[slot] : (uint32_t)slot;
+}
+template <class I>
+__device__ __forceinline__ bool skip_clean(const uint8_t* __restrict__ only_dirty, const uint32_t* __restrict__ store_slot, I slot)
+{
+    return only_dirty && !only_dirty[stored_at(store_slot, slot)];
+}
+// contributions [k0, k1) of a list dealt out to one wavefront: lane l adds k0 + l, k0 + l + 64, ... to its acc (the caller reduces across the wave)
+__device__ __forceinline__ void sum_list_strided(uint32_t k0, uint32_t k1, int lane, const uint32_t* __restrict__ sorted_src, const double* __restrict__ elemH,
+                                                 const float* __restrict__ elemHf, double* acc)
+{
+    for (uint32_t k = k0 + lane; k < k1; k += 64) {
+        const uint32_t src = sorted_src[k];
+        if (src == NO_SRC) continue;
+#pragma unroll
+        for (int c = 0; c < 9; c++) acc[c] += contrib(elemH, elemHf, src, c, (c % 3) * 3 + c / 3);
+    }
+}
 // one wavefront per long block (e.g. the diagonal block of a rigid body touched by thousands of contacts): lanes take
 // contributions k0 + lane, k0 + lane + 64, ... and the nine sums are reduced across the wave; the order is fixed by the sorted keys
 __global__ __launch_bounds__(BLOCK) void k_assemble_long(const double* __restrict__ elemH, const float* __restrict__ elemHf, const uint32_t* __restrict__ slot_start,
@@ -138,19 +167,13 @@ __global__ __launch_bounds__(BLOCK) void k_assemble_long(const double* __restric
     if (w >= n_long) return;
     const int lane = threadIdx.x & 63;
     const uint32_t slot = list[w];
-    if (only_dirty && !only_dirty[store_slot ? store_slot[slot] : slot]) return;  // (flags are indexed like the values: by storage position)
-    const uint32_t k0 = slot_start[slot], k1 = slot_start[slot + 1];
+    if (skip_clean(only_dirty, store_slot, slot)) return;
     double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t k = k0 + lane; k < k1; k += 64) {
-        const uint32_t src = sorted_src[k];
-        if (src == NO_SRC) continue;
-#pragma unroll
-        for (int c = 0; c < 9; c++) acc[c] += contrib(elemH, elemHf, src, c, (c % 3) * 3 + c / 3);
-    }
+    sum_list_strided(slot_start[slot], slot_start[slot + 1], lane, sorted_src, elemH, elemHf, acc);
 #pragma unroll
     for (int c = 0; c < 9; c++) {
         const double v = wave_sum(acc[c]);
-        if (lane == 0) vals[tile_val_index(store_slot ? store_slot[slot] : slot, c)] = (float)v;
+        if (lane == 0) vals[tile_val_index(stored_at(store_slot, slot), c)] = (float)v;
     }
 }
 // very long blocks: VLONG_SPLIT wavefronts per block sum contiguous ranges of its contribution list, a second pass adds the partial sums in
@@ -165,17 +188,12 @@ __global__ __launch_bounds__(BLOCK) void k_assemble_vlong_part(const double* __r
     const int lane = threadIdx.x & 63;
     const int b = w / VLONG_SPLIT, j = w - b * VLONG_SPLIT;
     const uint32_t slot = list[b];
-    if (only_dirty && !only_dirty[store_slot ? store_slot[slot] : slot]) return;
+    if (skip_clean(only_dirty, store_slot, slot)) return;
     const uint32_t k0 = slot_start[slot], k1 = slot_start[slot + 1];
     const uint32_t chunk = (k1 - k0 + VLONG_SPLIT - 1) / VLONG_SPLIT;
-    const uint32_t c0 = k0 + (uint32_t)j * chunk, c1 = min(k1, c0 + chunk);
+    const uint32_t c0 = k0 + (uint32_t)j * chunk;
     double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t k = c0 + lane; k < c1; k += 64) {
-        const uint32_t src = sorted_src[k];
-        if (src == NO_SRC) continue;
-#pragma unroll
-        for (int c = 0; c < 9; c++) acc[c] += contrib(elemH, elemHf, src, c, (c % 3) * 3 + c / 3);
-    }
+    sum_list_strided(c0, min(k1, c0 + chunk), lane, sorted_src, elemH, elemHf, acc);
 #pragma unroll
     for (int c = 0; c < 9; c++) {
         const double v = wave_sum(acc[c]);
@@ -190,11 +208,11 @@ __global__ __launch_bounds__(BLOCK) void k_assemble_vlong_fold(const double* __r
     const int lane = threadIdx.x & 63;
     static_assert(VLONG_SPLIT == 64, "one lane per partial sum");
     const uint32_t slot = list[b];
-    if (only_dirty && !only_dirty[store_slot ? store_slot[slot] : slot]) return;
+    if (skip_clean(only_dirty, store_slot, slot)) return;
 #pragma unroll
     for (int c = 0; c < 9; c++) {
         const double v = wave_sum(part[((size_t)b * VLONG_SPLIT + lane) * 9 + c]);
-        if (lane == 0) vals[tile_val_index(store_slot ? store_slot[slot] : slot, c)] = (float)v;
+        if (lane == 0) vals[tile_val_index(stored_at(store_slot, slot), c)] = (float)v;
     }
 }
 // One lane per BSR block: nine double accumulators, the contributions of the block summed in list order (deterministic, one float
@@ -222,20 +240,11 @@ __device__ __forceinline__ void store_block(float* __restrict__ vals, uint32_t p
         t2[512 + l2] = (float)acc[8];
     }
 }
-__global__ __launch_bounds__(BLOCK) void k_assemble_gather(const double* __restrict__ elemH, const float* __restrict__ elemHf, const uint32_t* __restrict__ slot_start,
-                                                           const uint32_t* __restrict__ sorted_src, int64_t nnzb, const uint32_t* __restrict__ store_slot, float* __restrict__ vals,
-                                                           const uint8_t* __restrict__ only_dirty, const uint32_t* __restrict__ sym)
+// contributions [k0, k1) of a list added to acc in list order, four in flight: the float pool's blocks are loaded branch-free (see contrib), the
+// double pool's only where a group of four has one
+__device__ __forceinline__ void sum_list4(uint32_t k0, uint32_t k1, const uint32_t* __restrict__ sorted_src, const double* __restrict__ elemH, const float* __restrict__ elemHf,
+                                          double* acc)
 {
-    const int64_t slot = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (slot >= nnzb) return;
-    if (only_dirty && !only_dirty[store_slot ? store_slot[slot] : (uint32_t)slot]) return;  // (project(): only the blocks a projection round touched; flags by storage position)
-    // (sym: block (i, j) of the static part whose contributions all come from the tets' float pool is the transpose of block (j, i) — the same pool
-    // blocks, read the other way round: the lane of the upper one writes both, the lower one's lane leaves at once; see k_sym_classify)
-    const uint32_t mirror = sym ? sym[slot] : SYM_NONE;
-    if (mirror == SYM_SKIP) return;
-    const uint32_t k0 = slot_start[slot], k1 = slot_start[slot + 1];
-    if (k1 - k0 > LONG_SLOT) return;  // k_assemble_long
-    double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (uint32_t kb = k0; kb < k1; kb += 4) {
         uint32_t d[4];
         F3 v[4][3];
@@ -277,8 +286,23 @@ __global__ __launch_bounds__(BLOCK) void k_assemble_gather(const double* __restr
             }
         }
     }
-    const uint32_t pos = store_slot ? store_slot[slot] : (uint32_t)slot;
-    store_block(vals, pos, mirror, acc);
+}
+__global__ __launch_bounds__(BLOCK) void k_assemble_gather(const double* __restrict__ elemH, const float* __restrict__ elemHf, const uint32_t* __restrict__ slot_start,
+                                                           const uint32_t* __restrict__ sorted_src, int64_t nnzb, const uint32_t* __restrict__ store_slot, float* __restrict__ vals,
+                                                           const uint8_t* __restrict__ only_dirty, const uint32_t* __restrict__ sym)
+{
+    const int64_t slot = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (slot >= nnzb) return;
+    if (skip_clean(only_dirty, store_slot, slot)) return;  // (project(): only the blocks a projection round touched)
+    // (sym: block (i, j) of the static part whose contributions all come from the tets' float pool is the transpose of block (j, i) — the same pool
+    // blocks, read the other way round: the lane of the upper one writes both, the lower one's lane leaves at once; see k_sym_classify)
+    const uint32_t mirror = sym ? sym[slot] : SYM_NONE;
+    if (mirror == SYM_SKIP) return;
+    const uint32_t k0 = slot_start[slot], k1 = slot_start[slot + 1];
+    if (k1 - k0 > LONG_SLOT) return;  // k_assemble_long
+    double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    sum_list4(k0, k1, sorted_src, elemH, elemHf, acc);
+    store_block(vals, stored_at(store_slot, slot), mirror, acc);
 }
 // ---- the same sums with the wavefront's long lists dealt out (round 5) ----------------------------------------------------------------------
 // k_assemble_gather is bound by instruction issue, not by memory: a wavefront of 64 consecutive blocks holds about four diagonal blocks whose
@@ -335,48 +359,8 @@ __global__ __launch_bounds__(BLOCK) void k_assemble_gather_split(const double* _
     const bool is_long = len > SPLIT_LEN;
     if (active && !is_long) {  // own short list: the four-way loop of k_assemble_gather
         double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t kb = k0; kb < k1; kb += 4) {
-            uint32_t d[4];
-            F3 v[4][3];
-#pragma unroll
-            for (int u = 0; u < 4; u++) d[u] = kb + u < k1 ? sorted_src[kb + u] : NO_SRC;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const bool f = d[u] != NO_SRC && (d[u] & DESC_FLOAT) != 0u;
-                const F3* src = reinterpret_cast<const F3*>(elemHf + (f ? (size_t)(d[u] & DESC_MASK) * 9 : (size_t)0));
-                v[u][0] = src[0];
-                v[u][1] = src[1];
-                v[u][2] = src[2];
-            }
-            bool any_double = false;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const bool f = d[u] != NO_SRC && (d[u] & DESC_FLOAT) != 0u;
-                const bool t = (d[u] & DESC_TRANS) != 0u;
-                any_double = any_double || (d[u] != NO_SRC && !f);
-                if (f) {
-                    acc[0] += (double)v[u][0].x;
-                    acc[1] += (double)(t ? v[u][1].x : v[u][0].y);
-                    acc[2] += (double)(t ? v[u][2].x : v[u][0].z);
-                    acc[3] += (double)(t ? v[u][0].y : v[u][1].x);
-                    acc[4] += (double)v[u][1].y;
-                    acc[5] += (double)(t ? v[u][2].y : v[u][1].z);
-                    acc[6] += (double)(t ? v[u][0].z : v[u][2].x);
-                    acc[7] += (double)(t ? v[u][1].z : v[u][2].y);
-                    acc[8] += (double)v[u][2].z;
-                }
-            }
-            if (any_double) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    if (d[u] == NO_SRC || (d[u] & DESC_FLOAT)) continue;
-                    const double* h = elemH + (size_t)d[u] * 9;
-#pragma unroll
-                    for (int c = 0; c < 9; c++) acc[c] += h[c];
-                }
-            }
-        }
-        store_block(vals, store_slot ? store_slot[slot] : (uint32_t)slot, mirror, acc);
+        sum_list4(k0, k1, sorted_src, elemH, elemHf, acc);
+        store_block(vals, stored_at(store_slot, slot), mirror, acc);
     }
     // the wavefront's long lists, eight at a time
     unsigned long long todo = __ballot(is_long);
@@ -403,7 +387,7 @@ __global__ __launch_bounds__(BLOCK) void k_assemble_gather_split(const double* _
         }
         if (has && sub == 0) {
             const int64_t gs = slot - lane + src;
-            store_block(vals, store_slot ? store_slot[gs] : (uint32_t)gs, g_mirror, a);
+            store_block(vals, stored_at(store_slot, gs), g_mirror, a);
         }
     }
 }
@@ -1149,11 +1133,7 @@ double spmv_bench(Context& c, int n)
     return 1000.0 * ms / n;
 }
 
-void spmv_device(Context& c, const double* x, double* y, const double* pdot, double* partials, bool timed)
-{
-    (void)timed;
-    launch_spmv<0>(c, x, y, pdot, partials, nullptr);
-}
+void spmv_device(Context& c, const double* x, double* y, const double* pdot, double* partials) { launch_spmv<0>(c, x, y, pdot, partials, nullptr); }
 
 // ======================================================================================================================
 // PCG (BlockedSparseMatrix/solve_pcg.h:83-232), x0 = 0. Iteration k = 1..max_iter is three launches:
@@ -1162,6 +1142,36 @@ void spmv_device(Context& c, const double* x, double* y, const double* pdot, dou
 //   k_pcg_dir   error = sqrt(rr/bb); convergence test; beta = rz'/rz; p = z + beta p
 // Scalars never leave the device inside the loop; `ctrl->done` turns the remaining launches of a batch into no-ops.
 // ======================================================================================================================
+// z = D^-1 r for one block row (row- or column-major alike: the inverse is symmetric)
+__device__ __forceinline__ double3 apply_dinv(const float* d, double r0, double r1, double r2)
+{
+    return make_double3((double)d[0] * r0 + (double)d[1] * r1 + (double)d[2] * r2, (double)d[3] * r0 + (double)d[4] * r1 + (double)d[5] * r2,
+                        (double)d[6] * r0 + (double)d[7] * r1 + (double)d[8] * r2);
+}
+// the control block at the start of a solve; ctrl_reset: with the two exits before the first iteration
+__device__ __forceinline__ void ctrl_clear(PcgCtrl* __restrict__ ctrl, double bb, double rz)
+{
+    ctrl->bb = bb;
+    ctrl->rz[1] = rz;
+    ctrl->rz[0] = 0.0;
+    ctrl->indef = 0;
+    ctrl->n_iter = 0;
+    ctrl->converged = 0;
+    ctrl->done = 0;
+    ctrl->error = 1.0;  // r = b  =>  error_0 = 1
+}
+__device__ __forceinline__ void ctrl_reset(PcgCtrl* __restrict__ ctrl, double bb, double rz, double abs_tol)
+{
+    ctrl_clear(ctrl, bb, rz);
+    if (bb < abs_tol * abs_tol) {  // zero right-hand side (solve_pcg.h:125-131)
+        ctrl->done = 1;
+        ctrl->converged = 1;
+        ctrl->error = 0.0;
+    } else if (1.0 < abs_tol) {    // initial residual already below tolerance (:150-156)
+        ctrl->done = 1;
+        ctrl->converged = 1;
+    }
+}
 __global__ __launch_bounds__(BLOCK) void k_pcg_init(const double* __restrict__ b, const float* __restrict__ dinv, int64_t nbr, double* __restrict__ x, double* __restrict__ r,
                                                     double* __restrict__ z, double* __restrict__ p, double* __restrict__ part_bb, double* __restrict__ part_rz)
 {
@@ -1169,11 +1179,8 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_init(const double* __restrict__ b
     double bb = 0.0, rz = 0.0;
     for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < nbr; row += (int64_t)gridDim.x * BLOCK) {
         const double r0 = b[3 * row], r1 = b[3 * row + 1], r2 = b[3 * row + 2];
-        const float* d = dinv + 9 * row;
-        // column-major-agnostic: the inverse is symmetric
-        const double z0 = (double)d[0] * r0 + (double)d[1] * r1 + (double)d[2] * r2;
-        const double z1 = (double)d[3] * r0 + (double)d[4] * r1 + (double)d[5] * r2;
-        const double z2 = (double)d[6] * r0 + (double)d[7] * r1 + (double)d[8] * r2;
+        const double3 zz = apply_dinv(dinv + 9 * row, r0, r1, r2);
+        const double z0 = zz.x, z1 = zz.y, z2 = zz.z;
         x[3 * row] = 0.0; x[3 * row + 1] = 0.0; x[3 * row + 2] = 0.0;
         r[3 * row] = r0; r[3 * row + 1] = r1; r[3 * row + 2] = r2;
         z[3 * row] = z0; z[3 * row + 1] = z1; z[3 * row + 2] = z2;
@@ -1202,24 +1209,15 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_prologue(const double* __restrict
     double bb = 0.0, rz = 0.0;
     for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < nbr; row += (int64_t)gridDim.x * BLOCK) {
         float m[9], d[9];
-        const uint32_t s = (uint32_t)diag_slot[row];
-#pragma unroll
-        for (int k = 0; k < 9; k++) m[k] = vals[tile_val_index(s, k)];
-        if (vals_dyn) {
-            const int32_t sd = diag_slot_dyn[row];
-            if (sd >= 0) {
-#pragma unroll
-                for (int k = 0; k < 9; k++) m[k] += vals_dyn[tile_val_index((uint32_t)sd, k)];
-            }
-        }
+        load_diag_block(vals, diag_slot, vals_dyn, diag_slot_dyn, row, m);
         sym3_inverse(m, d);
 #pragma unroll
         for (int k = 0; k < 9; k++) dinv[9 * row + k] = d[k];
         const int64_t g = src_row ? (int64_t)src_row[row] : row;
+        // (from here k_pcg_init's row body, written out in both: behind a shared helper the compiler orders the loads of both kernels differently)
         const double r0 = scale * rhs[3 * g], r1 = scale * rhs[3 * g + 1], r2 = scale * rhs[3 * g + 2];
-        const double z0 = (double)d[0] * r0 + (double)d[1] * r1 + (double)d[2] * r2;
-        const double z1 = (double)d[3] * r0 + (double)d[4] * r1 + (double)d[5] * r2;
-        const double z2 = (double)d[6] * r0 + (double)d[7] * r1 + (double)d[8] * r2;
+        const double3 zz = apply_dinv(d, r0, r1, r2);
+        const double z0 = zz.x, z1 = zz.y, z2 = zz.z;
         x[3 * row] = 0.0; x[3 * row + 1] = 0.0; x[3 * row + 2] = 0.0;
         r[3 * row] = r0; r[3 * row + 1] = r1; r[3 * row + 2] = r2;
         z[3 * row] = z0; z[3 * row + 1] = z1; z[3 * row + 2] = z2;
@@ -1263,24 +1261,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_init2(const double* __restrict__ 
     __shared__ double sm[4];
     const double bb = sum_partials(part_bb, nparts, sm, stride);
     const double rz = sum_partials(part_rz, nparts, sm, stride);
-    if (threadIdx.x == 0) {
-        ctrl->bb = bb;
-        ctrl->rz[1] = rz;
-        ctrl->rz[0] = 0.0;
-        ctrl->indef = 0;
-        ctrl->n_iter = 0;
-        ctrl->converged = 0;
-        ctrl->done = 0;
-        ctrl->error = 1.0;  // r = b  =>  error_0 = 1
-        if (bb < abs_tol * abs_tol) {  // zero right-hand side (solve_pcg.h:125-131)
-            ctrl->done = 1;
-            ctrl->converged = 1;
-            ctrl->error = 0.0;
-        } else if (1.0 < abs_tol) {    // initial residual already below tolerance (:150-156)
-            ctrl->done = 1;
-            ctrl->converged = 1;
-        }
-    }
+    if (threadIdx.x == 0) ctrl_reset(ctrl, bb, rz, abs_tol);
 }
 // (The loads of a thread's first block row are issued BEFORE the reduction of the partial sums every workgroup starts with: that
 // reduction is a chain of dependent steps of 1.5-2 us during which the memory system would otherwise idle; with one row per thread, which is
@@ -1345,10 +1326,8 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_step(int k, int stop_on_indef, co
             x[i + 1] = w.x1 + alpha * w.p1;
             x[i + 2] = w.x2 + alpha * w.p2;
             r[i] = r0; r[i + 1] = r1; r[i + 2] = r2;
-            const float* d = w.d;
-            const double z0 = (double)d[0] * r0 + (double)d[1] * r1 + (double)d[2] * r2;
-            const double z1 = (double)d[3] * r0 + (double)d[4] * r1 + (double)d[5] * r2;
-            const double z2 = (double)d[6] * r0 + (double)d[7] * r1 + (double)d[8] * r2;
+            const double3 zz = apply_dinv(w.d, r0, r1, r2);
+            const double z0 = zz.x, z1 = zz.y, z2 = zz.z;
             z[i] = z0; z[i + 1] = z1; z[i + 2] = z2;
             rr += r0 * r0 + r1 * r1 + r2 * r2;
             rzn += r0 * z0 + r1 * z1 + r2 * z2;
@@ -1492,32 +1471,22 @@ __device__ __forceinline__ void ghosts_from_gathered(const double* __restrict__ 
         *pg = beta == 0.0 ? zg : zg + beta * *pg;
     }
 }
+// the ranks' two scalars at the head of their parts of a gathered buffer (stride S), added in rank order: the same bits on every rank
+__device__ __forceinline__ void rank_sum2(const double* __restrict__ recv, int W, int64_t S, double& a, double& b)
+{
+    a = 0.0;
+    b = 0.0;
+    for (int r = 0; r < W; r++) {
+        a += recv[r * S];
+        b += recv[r * S + 1];
+    }
+}
 __global__ __launch_bounds__(BLOCK) void k_pcg_init2_sharded(const double* __restrict__ recv, int W, int64_t S, double abs_tol, PcgCtrl* __restrict__ ctrl, const int32_t* __restrict__ ghost_src,
                                                              int64_t send_stride, int64_t n_ghost, int64_t n_own, double* __restrict__ p)
 {
-    double bb = 0.0, rz = 0.0;
-    for (int r = 0; r < W; r++) {  // rank order: the same bits on every rank
-        bb += recv[r * S];
-        rz += recv[r * S + 1];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctrl->bb = bb;
-        ctrl->rz[1] = rz;
-        ctrl->rz[0] = 0.0;
-        ctrl->indef = 0;
-        ctrl->n_iter = 0;
-        ctrl->converged = 0;
-        ctrl->done = 0;
-        ctrl->error = 1.0;
-        if (bb < abs_tol * abs_tol) {
-            ctrl->done = 1;
-            ctrl->converged = 1;
-            ctrl->error = 0.0;
-        } else if (1.0 < abs_tol) {
-            ctrl->done = 1;
-            ctrl->converged = 1;
-        }
-    }
+    double bb, rz;
+    rank_sum2(recv, W, S, bb, rz);
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl_reset(ctrl, bb, rz, abs_tol);
     ghosts_from_gathered(recv, S, ghost_src, send_stride, n_ghost, n_own, 0.0, p);  // p_0 = z_0 on the ghosts too
 }
 __global__ __launch_bounds__(BLOCK) void k_pcg_dir_sharded(int k, double abs_tol, double rel_tol, const double* __restrict__ recv, int W, int64_t S, int64_t n, const double* __restrict__ z,
@@ -1530,11 +1499,8 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_dir_sharded(int k, double abs_tol
         if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->done = 1;
         return;
     }
-    double rr = 0.0, rz_new = 0.0;
-    for (int r = 0; r < W; r++) {
-        rr += recv[r * S];
-        rz_new += recv[r * S + 1];
-    }
+    double rr, rz_new;
+    rank_sum2(recv, W, S, rr, rz_new);
     const double error = sqrt(rr / ctrl->bb);
     const bool conv = error < abs_tol || error / 1.0 < rel_tol;
     if (conv) {
@@ -1555,6 +1521,171 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_dir_sharded(int k, double abs_tol
         ctrl->n_iter = k;
     }
 }
+// ---- what the host side of the PCG drivers below shares ----------------------------------------------------------------------------------------
+static double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// the result of a solve from the control block the host read last
+static void finish_solve(Context& c, const PcgCtrl& h, int max_iter, mistark_pcg_info* info)
+{
+    const int n_it = h.done ? h.n_iter : max_iter;
+    c.last_cg_iters = n_it;
+    if (info) {
+        info->converged = h.done ? h.converged : 0;
+        info->n_iterations = n_it;
+        info->found_indefiniteness = h.indef;
+        info->error = h.error;
+        info->reserved = 0;
+    }
+}
+// SpMV timing inside the solvers, for the bench's roofline figure: a sampled launch writes per-workgroup (start, end) stamps of the device clock to
+// pinned memory (begin() returns the buffer to hand to the launch) and — events — is bracketed by a pair of pooled HIP events on the engine's stream
+// with an empty bracket right behind: what a pair of event records costs the stream by itself (the marker packets' own processing is inside every
+// bracketed duration; bench.py reports both figures). A sampled launch costs the stream ~14 us of marker packets: 1.3 % of the timed region at
+// every 16th launch, measured; the drivers sample one launch in SPMV_SAMPLE.
+constexpr int SPMV_SAMPLE = 32;
+struct SpmvSampler
+{
+    Context& c;
+    uint64_t*& buf;  // pinned clock stamps, allocated at the first sample: `cap` samples of 2 * MAX_PARTIALS
+    size_t cap;
+    size_t first;    // this set's first place in the buffer and in the event pool
+    bool events;
+    std::vector<int> at, grid;  // iteration and SpMV grid of the samples taken
+    size_t size() const { return at.size(); }
+    void clear()
+    {
+        at.clear();
+        grid.clear();
+    }
+    // in front of the sampled launch of iteration k: the clock buffer to hand to it
+    uint64_t* begin(int k)
+    {
+        const size_t i = first + at.size();
+        if (events) {
+            while (c.ev.size() < 3 * (i + 1)) {
+                hipEvent_t e;
+                MS_CHECK(hipEventCreate(&e));
+                c.ev.push_back(e);
+            }
+            MS_CHECK(hipEventRecord(c.ev[3 * i], c.stream));
+        }
+        if (!buf) MS_CHECK(hipHostMalloc((void**)&buf, sizeof(uint64_t) * cap * 2 * MAX_PARTIALS, hipHostMallocDefault));
+        uint64_t* clk = buf + i * 2 * MAX_PARTIALS;
+        std::memset(clk, 0, sizeof(uint64_t) * 2 * MAX_PARTIALS);
+        at.push_back(k);
+        return clk;
+    }
+    // behind it (gs: its grid)
+    void end(int gs)
+    {
+        const size_t i = first + grid.size();
+        if (events) {
+            MS_CHECK(hipEventRecord(c.ev[3 * i + 1], c.stream));
+            MS_CHECK(hipEventRecord(c.ev[3 * i + 2], c.stream));
+        }
+        grid.push_back(gs);
+    }
+    // once the stream has passed the samples: the ones up to iteration last_real into the context's sums (behind it: no-op launches after the
+    // solve was over)
+    void fold(int last_real)
+    {
+        for (size_t j = 0; j < at.size(); j++) {
+            if (at[j] > last_real) continue;
+            const size_t i = first + j;
+            float ms = 0.f, ms_empty = 0.f;
+            if (events && hipEventElapsedTime(&ms, c.ev[3 * i], c.ev[3 * i + 1]) == hipSuccess && hipEventElapsedTime(&ms_empty, c.ev[3 * i + 1], c.ev[3 * i + 2]) == hipSuccess) {
+                c.spmv_ms_sum += ms;
+                c.spmv_empty_ms_sum += ms_empty;
+                c.spmv_n++;
+            }
+            const uint64_t* clk = buf + i * 2 * MAX_PARTIALS;
+            uint64_t t0 = ~0ull, t1 = 0;
+            bool complete = true;
+            for (int b = 0; b < grid[j]; b++) {
+                if (clk[2 * b] == 0 || clk[2 * b + 1] == 0) { complete = false; break; }
+                t0 = std::min(t0, clk[2 * b]);
+                t1 = std::max(t1, clk[2 * b + 1]);
+            }
+            if (complete && t1 > t0) {
+                c.spmv_clk_ticks += (double)(t1 - t0);
+                c.spmv_clk_n++;
+            }
+        }
+    }
+};
+constexpr size_t SHARDED_SAMPLES = 64;  // most samples of a sharded solve
+// The wait for the pinned slot a batch's last kernel writes the control block to (publish_ctrl): the host watches the slot itself — an event
+// record between batches is a marker packet the next SpMV waits behind: 5 us per batch. Now and then a real look at the stream, as publish()
+// does: a failed launch surfaces as its error, and a stream that has drained without the slot being written (host memory the device's writes do
+// not reach while kernels run) is answered from the device's own control block instead of a time-out. what: "<driver>: the device did not
+// report <iteration | batch>".
+static PcgCtrl wait_for_batch(Context& c, PcgCtrl* slot, int epoch, int k_end, double timeout_s, const char* what)
+{
+    const volatile PcgCtrl* v = slot;
+    const double t_wait = now_seconds();
+    auto reported = [&] { return v->epoch == epoch && (v->done || v->n_iter >= k_end); };
+    for (uint64_t spins = 0; !reported(); spins++) {
+        __builtin_ia32_pause();
+        if ((spins & 0xfffff) != 0xfffff) continue;
+        if (c.coll) c.coll->check();  // (ranks on windows: a peer that gave up)
+        const hipError_t q = hipStreamQuery(c.stream);
+        if (q != hipErrorNotReady) {
+            MS_CHECK(q);
+            if (!reported()) {
+                PcgCtrl dev{};
+                MS_CHECK(hipMemcpy(&dev, c.ctrl.p, sizeof(PcgCtrl), hipMemcpyDeviceToHost));
+                slot->converged = dev.converged;
+                slot->indef = dev.indef;
+                slot->error = dev.error;
+                slot->n_iter = dev.done ? dev.n_iter : k_end;
+                slot->done = dev.done ? 1 : 0;
+                slot->epoch = epoch;
+            }
+            break;
+        }
+        if (now_seconds() - t_wait > timeout_s) throw Error(std::string(what) + " " + std::to_string(k_end) + " within " + std::to_string((int)timeout_s) + " s");
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return *slot;
+}
+// Iterations are launched in batches; the last kernel of a batch writes the control block to a pinned slot. The host launches batch b+1
+// BEFORE it waits for batch b's slot, so the GPU never idles on the host's convergence check, and at most one batch of device-side no-op
+// launches (ctrl->done) is wasted after convergence; later work queues behind it on the same stream.
+//   launch_batch(slot, host_slot, epoch) -> the batch's last iteration   more() -> there is another batch to launch
+//   after_wait(slot, h, k_end): the control block of the batch that ended at k_end has been read
+// Returns the control block the solve ended with.
+template <class Launch, class More, class AfterWait>
+static PcgCtrl run_batches(Context& c, double timeout_s, const char* what, Launch launch_batch, More more, AfterWait after_wait)
+{
+    PcgCtrl* hs[2] = {reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048), reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048 + 64)};  // pinned
+    const int epoch = ++c.pcg_epoch;
+    auto launch = [&](int slot) {
+        hs[slot]->epoch = epoch - 1;  // (whatever a straggler of the previous solve writes here carries the previous epoch, too)
+        hs[slot]->done = 0;
+        hs[slot]->n_iter = -1;
+        return launch_batch(slot, hs[slot], epoch);
+    };
+    int slot = 0;
+    int k_end_cur = launch(0);
+    for (;;) {
+        const bool another = more();
+        const int k_end_next = another ? launch(slot ^ 1) : 0;  // keep the GPU fed while the host looks at the previous batch
+        const PcgCtrl h = wait_for_batch(c, hs[slot], epoch, k_end_cur, timeout_s, what);
+        after_wait(slot, h, k_end_cur);
+        if (h.done || !another) return h;
+        slot ^= 1;
+        k_end_cur = k_end_next;
+    }
+}
+// the solver's prologue on one GPU: k_pcg_prologue and the fold of its partial sums into the control block
+static void launch_prologue(Context& c, const double* rhs_dev, double rhs_scale, int gv, double abs_tol, double* x, double* r, double* z, double* p, double* part_bb, double* part_rz)
+{
+    const BsrPart& d1 = c.part[1];
+    hipLaunchKernelGGL(k_pcg_prologue, dim3(gv), dim3(BLOCK), 0, c.stream, rhs_dev, rhs_scale, (const float*)c.part[0].vals.p, (const int32_t*)c.diag_slot[0].p,
+                       d1.nnzb ? (const float*)d1.vals.p : (const float*)nullptr, (const int32_t*)c.diag_slot[1].p, c.nbr, c.dinv.p, x, r, z, p, part_bb, part_rz,
+                       c.perm_active ? (const int32_t*)c.iperm.p : (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_pcg_init2, dim3(1), dim3(BLOCK), 0, c.stream, part_bb, part_rz, gv, abs_tol, c.ctrl.p, 1);
+}
+
 static void pcg_sharded(Context& c, const double* rhs_global, double abs_tol, double rel_tol, int max_iter, int stop_on_indef, mistark_pcg_info* info)
 {
     Shard& S = c.sh;
@@ -1590,33 +1721,13 @@ static void pcg_sharded(Context& c, const double* rhs_global, double abs_tol, do
     PcgCtrl h{};
     int k = 1;
     bool finished = false;
-    std::vector<int> sampled_k, sampled_grid;
+    SpmvSampler smp{c, c.spmv_clk_sharded, SHARDED_SAMPLES, 0, true};
     while (!finished) {
         const int k_end = std::min(max_iter, k + PCG_CHECK - 1);
         for (; k <= k_end; k++) {
-            // (SpMV timing for the bench's roofline figure, as in pcg(): one launch in 32 between a pair of events, an empty pair behind it)
-            const bool sample = c.time_spmv && (k % 32) == 0 && sampled_k.size() < 64;
-            if (sample) {
-                while (c.ev.size() < 3 * (sampled_k.size() + 1)) {
-                    hipEvent_t e;
-                    MS_CHECK(hipEventCreate(&e));
-                    c.ev.push_back(e);
-                }
-                MS_CHECK(hipEventRecord(c.ev[3 * sampled_k.size()], c.stream));
-            }
-            uint64_t* clk = nullptr;
-            if (sample) {  // (and on the device clock, as in pcg(): per-workgroup start / end stamps in pinned memory)
-                if (!c.spmv_clk_sharded) MS_CHECK(hipHostMalloc((void**)&c.spmv_clk_sharded, sizeof(uint64_t) * 64 * 2 * MAX_PARTIALS, hipHostMallocDefault));
-                clk = c.spmv_clk_sharded + sampled_k.size() * 2 * MAX_PARTIALS;
-                std::memset(clk, 0, sizeof(uint64_t) * 2 * MAX_PARTIALS);
-            }
-            const int gs = launch_spmv<0>(c, c.p.p, c.q.p, c.p.p, part_pq, c.ctrl.p, /*combine=*/false, clk);
-            if (sample) {
-                MS_CHECK(hipEventRecord(c.ev[3 * sampled_k.size() + 1], c.stream));
-                MS_CHECK(hipEventRecord(c.ev[3 * sampled_k.size() + 2], c.stream));
-                sampled_k.push_back(k);
-                sampled_grid.push_back(gs);
-            }
+            const bool sample = c.time_spmv && (k % SPMV_SAMPLE) == 0 && smp.size() < SHARDED_SAMPLES;
+            const int gs = launch_spmv<0>(c, c.p.p, c.q.p, c.p.p, part_pq, c.ctrl.p, /*combine=*/false, sample ? smp.begin(k) : nullptr);
+            if (sample) smp.end(gs);
             hipLaunchKernelGGL(k_fold_partials, dim3(1), dim3(BLOCK), 0, c.stream, (const double*)part_pq, gs, (const double*)nullptr, 0, mine1);
             c.coll->allgather_f64(mine1, all1, 1, c.stream);
             hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(BLOCK), 0, c.stream, k, stop_on_indef, (const double*)all1, W, c.dinv.p, n_own, c.p.p, c.q.p, c.xl.p, c.r.p, c.z.p, part_rr,
@@ -1631,37 +1742,9 @@ static void pcg_sharded(Context& c, const double* rhs_global, double abs_tol, do
         fetch(c, &h, c.ctrl.p, sizeof(PcgCtrl));
         finished = h.done || k > max_iter;
     }
-    for (size_t i = 0; i < sampled_k.size(); i++) {  // (the fetch above waited for the stream)
-        if (h.done && sampled_k[i] > h.n_iter) continue;  // a no-op launch after convergence
-        float ms = 0.f, ms_empty = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[3 * i], c.ev[3 * i + 1]) == hipSuccess && hipEventElapsedTime(&ms_empty, c.ev[3 * i + 1], c.ev[3 * i + 2]) == hipSuccess) {
-            c.spmv_ms_sum += ms;
-            c.spmv_empty_ms_sum += ms_empty;
-            c.spmv_n++;
-        }
-        const uint64_t* clk = c.spmv_clk_sharded + i * 2 * MAX_PARTIALS;
-        uint64_t t0 = ~0ull, t1 = 0;
-        bool complete = true;
-        for (int b = 0; b < sampled_grid[i]; b++) {
-            if (clk[2 * b] == 0 || clk[2 * b + 1] == 0) { complete = false; break; }
-            t0 = std::min(t0, clk[2 * b]);
-            t1 = std::max(t1, clk[2 * b + 1]);
-        }
-        if (complete && t1 > t0) {
-            c.spmv_clk_ticks += (double)(t1 - t0);
-            c.spmv_clk_n++;
-        }
-    }
+    smp.fold(h.done ? h.n_iter : max_iter);  // (the fetch above waited for the stream)
     shard_gather_global(c, c.xl.p, c.du.p);
-    const int n_it = h.done ? h.n_iter : max_iter;
-    c.last_cg_iters = n_it;
-    if (info) {
-        info->converged = h.done ? h.converged : 0;
-        info->n_iterations = n_it;
-        info->found_indefiniteness = h.indef;
-        info->error = h.error;
-        info->reserved = 0;
-    }
+    finish_solve(c, h, max_iter, info);
 }
 
 // ---- the row-sharded PCG with ONE exposed exchange per iteration, for ranks that exchange through windows (dist.hpp: IpcView) --------------
@@ -1717,10 +1800,8 @@ __global__ __launch_bounds__(BLOCK) void k_cg_prologue(CgFast f, uint32_t tag_ou
     for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < n_own; row += (int64_t)gridDim.x * BLOCK) {
         const size_t i = 3 * (size_t)row;
         const double r0 = b[i], r1 = b[i + 1], r2 = b[i + 2];
-        const float* d = dinv + 9 * row;
-        const double u0 = (double)d[0] * r0 + (double)d[1] * r1 + (double)d[2] * r2;
-        const double u1 = (double)d[3] * r0 + (double)d[4] * r1 + (double)d[5] * r2;
-        const double u2 = (double)d[6] * r0 + (double)d[7] * r1 + (double)d[8] * r2;
+        const double3 uu = apply_dinv(dinv + 9 * row, r0, r1, r2);
+        const double u0 = uu.x, u1 = uu.y, u2 = uu.z;
         x[i] = 0.0; x[i + 1] = 0.0; x[i + 2] = 0.0;
         p[i] = 0.0; p[i + 1] = 0.0; p[i + 2] = 0.0;
         s[i] = 0.0; s[i + 1] = 0.0; s[i + 2] = 0.0;
@@ -1738,14 +1819,8 @@ __global__ __launch_bounds__(BLOCK) void k_cg_prologue(CgFast f, uint32_t tag_ou
         part_rr[blockIdx.x] = bb;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctrl->bb = 0.0;
-        ctrl->rz[0] = ctrl->rz[1] = 0.0;
+        ctrl_clear(ctrl, 0.0, 0.0);  // (the first V writes bb and the two exits: k_cg_vec, i == 0)
         ctrl->alpha[0] = ctrl->alpha[1] = 0.0;
-        ctrl->indef = 0;
-        ctrl->n_iter = 0;
-        ctrl->converged = 0;
-        ctrl->done = 0;
-        ctrl->error = 1.0;
     }
 }
 struct VecRow
@@ -1897,10 +1972,8 @@ __global__ __launch_bounds__(BLOCK) void k_cg_vec(int k, int check_only, int sto
         s[j] = s0; s[j + 1] = s1; s[j + 2] = s2;
         x[j] = v.x0 + alpha * p0; x[j + 1] = v.x1 + alpha * p1; x[j + 2] = v.x2 + alpha * p2;
         r[j] = r0; r[j + 1] = r1; r[j + 2] = r2;
-        const float* d = v.d;
-        const double u0 = (double)d[0] * r0 + (double)d[1] * r1 + (double)d[2] * r2;
-        const double u1 = (double)d[3] * r0 + (double)d[4] * r1 + (double)d[5] * r2;
-        const double u2 = (double)d[6] * r0 + (double)d[7] * r1 + (double)d[8] * r2;
+        const double3 uu = apply_dinv(v.d, r0, r1, r2);
+        const double u0 = uu.x, u1 = uu.y, u2 = uu.z;
         u[j] = u0; u[j + 1] = u1; u[j + 2] = u2;
         rrn += r0 * r0 + r1 * r1 + r2 * r2;
         ru += r0 * u0 + r1 * u1 + r2 * u2;
@@ -1984,7 +2057,6 @@ __global__ __launch_bounds__(BLOCK) void k_spmv_halo(int g0, int gr, int g1, Sta
         }
     }
 }
-static double now_seconds();
 namespace {
 // want[owner * send_stride + position] = 1 for every ghost column the matrix references
 __global__ __launch_bounds__(BLOCK) void k_mark_ghost_refs(const uint32_t* __restrict__ colw, int64_t n, int64_t n_own, const int32_t* __restrict__ ghost_src, double* __restrict__ want)
@@ -2139,75 +2211,29 @@ static bool pcg_sharded_fused(Context& c, const double* rhs_global, double abs_t
     shard_to_local(c, rhs_global, b_l, false);
     hipLaunchKernelGGL(k_cg_prologue, dim3(F.gv), dim3(BLOCK), 0, c.stream, F.f, F.tag_m1(0), (const double*)b_l, (const float*)c.dinv.p, S.n_own, F.x, F.r, F.u, F.p, F.s, c.ctrl.p,
                        (const int32_t*)S.send_pos_of_row.p, F.send_mask, F.pr[0][0], F.pr[0][1]);
-    std::vector<int> sampled_i;
+    SpmvSampler smp{c, c.spmv_clk_sharded, SHARDED_SAMPLES, 0, false};  // (the device clock only)
     auto launch_S = [&](int i) {
-        uint64_t* clk = nullptr;
-        if (c.time_spmv && i > 0 && (i % 32) == 0 && sampled_i.size() < 64) {  // (device-clock sample for the bench's roofline figure, as in pcg())
-            if (!c.spmv_clk_sharded) MS_CHECK(hipHostMalloc((void**)&c.spmv_clk_sharded, sizeof(uint64_t) * 64 * 2 * MAX_PARTIALS, hipHostMallocDefault));
-            clk = c.spmv_clk_sharded + sampled_i.size() * 2 * MAX_PARTIALS;
-            std::memset(clk, 0, sizeof(uint64_t) * 2 * MAX_PARTIALS);
-            sampled_i.push_back(i);
-        }
-        F.launch_S(i, clk, 0);
+        const bool sample = c.time_spmv && i > 0 && (i % SPMV_SAMPLE) == 0 && smp.size() < SHARDED_SAMPLES;
+        F.launch_S(i, sample ? smp.begin(i) : nullptr, 0);
+        if (sample) smp.end(F.gs);
     };
-    // batches of [S_{k-1}, R_{k-1}, V_k] with one look-ahead batch in flight, as in pcg(): the last V of a batch writes the control block to a
-    // pinned slot the host watches
+    // batches of [S_{k-1}, V_k] with one look-ahead batch in flight: the last V of a batch writes the control block to the pinned slot
     constexpr int BATCH = 8;
-    PcgCtrl* hs[2] = {reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048), reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048 + 64)};
-    const int epoch = ++c.pcg_epoch;
     int k = 1;  // next V to launch
     bool tail_done = false;  // the check-only V behind iteration max_iter has been launched
-    auto launch_batch = [&](int slot) {
-        hs[slot]->epoch = epoch - 1;
-        hs[slot]->done = 0;
-        hs[slot]->n_iter = -1;
+    auto launch_batch = [&](int, PcgCtrl* host_slot, int epoch) {
         const int k_end = std::min(max_iter + 1, k + BATCH - 1);
         for (; k <= k_end; k++) {
             const bool check_only = k == max_iter + 1;
             launch_S(k - 1);      // w_{k-1}
-            F.launch_V(k, check_only, stop_on_indef, abs_tol, rel_tol, k == k_end ? hs[slot] : (PcgCtrl*)nullptr, epoch, 0);
+            F.launch_V(k, check_only, stop_on_indef, abs_tol, rel_tol, k == k_end ? host_slot : (PcgCtrl*)nullptr, epoch, 0);
             if (check_only) tail_done = true;
         }
         return k_end;
     };
-    PcgCtrl h{};
-    int slot = 0;
-    int k_end_cur = launch_batch(0);
-    for (;;) {
-        const bool more = !tail_done;
-        int k_end_next = 0;
-        if (more) k_end_next = launch_batch(slot ^ 1);
-        const volatile PcgCtrl* v = hs[slot];
-        const double t_wait = now_seconds();
-        auto reported = [&] { return v->epoch == epoch && (v->done || v->n_iter >= k_end_cur); };
-        for (uint64_t spins = 0; !reported(); spins++) {
-            __builtin_ia32_pause();
-            if ((spins & 0xfffff) != 0xfffff) continue;
-            c.coll->check();
-            const hipError_t q = hipStreamQuery(c.stream);
-            if (q != hipErrorNotReady) {
-                MS_CHECK(q);
-                if (!reported()) {
-                    PcgCtrl dev{};
-                    MS_CHECK(hipMemcpy(&dev, c.ctrl.p, sizeof(PcgCtrl), hipMemcpyDeviceToHost));
-                    hs[slot]->converged = dev.converged;
-                    hs[slot]->indef = dev.indef;
-                    hs[slot]->error = dev.error;
-                    hs[slot]->n_iter = dev.done ? dev.n_iter : k_end_cur;
-                    hs[slot]->done = dev.done ? 1 : 0;
-                    hs[slot]->epoch = epoch;
-                }
-                break;
-            }
-            if (now_seconds() - t_wait > 120.0) throw Error("sharded pcg: the device did not report iteration " + std::to_string(k_end_cur) + " within 120 s");
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        h = *hs[slot];
-        if (dbg) std::fprintf(stderr, "[fused r%d] batch to %d: done %d conv %d indef %d n_iter %d err %g (k next %d)\n", me, k_end_cur, h.done, h.converged, h.indef, h.n_iter, h.error, k);
-        if (h.done || !more) break;
-        slot ^= 1;
-        k_end_cur = k_end_next;
-    }
+    const PcgCtrl h = run_batches(c, 120.0, "sharded pcg: the device did not report iteration", launch_batch, [&] { return !tail_done; }, [&](int, const PcgCtrl& b, int k_end) {
+        if (dbg) std::fprintf(stderr, "[fused r%d] batch to %d: done %d conv %d indef %d n_iter %d err %g (k next %d)\n", me, k_end, b.done, b.converged, b.indef, b.n_iter, b.error, k);
+    });
     // the next solve's tags start behind the last one any rank can have used in this one (a rank launches at most two batches beyond the
     // iteration that ended the solve; computed from the iteration count, which is the same number on every rank)
     c.fused_tag = F.base + 2u * (uint32_t)((h.done ? h.n_iter : max_iter) + 2 * BATCH + 4);
@@ -2217,32 +2243,9 @@ static bool pcg_sharded_fused(Context& c, const double* rhs_global, double abs_t
     shard_gather_global(c, F.x, c.du.p);  // (also the barrier between this solve's last window readers and the next solve's first push)
     MS_CHECK(hipStreamSynchronize(c.stream));
     c.coll->check();
-    if (c.time_spmv) {
-        for (size_t q = 0; q < sampled_i.size(); q++) {
-            if (h.done && sampled_i[q] >= h.n_iter) continue;  // (a no-op launch after the solve was over)
-            const uint64_t* clk = c.spmv_clk_sharded + q * 2 * MAX_PARTIALS;
-            uint64_t t0 = ~0ull, t1 = 0;
-            bool complete = true;
-            for (int b = 0; b < F.gs; b++) {
-                if (clk[2 * b] == 0 || clk[2 * b + 1] == 0) { complete = false; break; }
-                t0 = std::min(t0, clk[2 * b]);
-                t1 = std::max(t1, clk[2 * b + 1]);
-            }
-            if (complete && t1 > t0) {
-                c.spmv_clk_ticks += (double)(t1 - t0);
-                c.spmv_clk_n++;
-            }
-        }
-    }
-    const int n_it = h.done ? h.n_iter : max_iter;
-    c.last_cg_iters = n_it;
-    if (info) {
-        info->converged = h.done ? h.converged : 0;
-        info->n_iterations = n_it;
-        info->found_indefiniteness = h.indef;
-        info->error = h.error;
-        info->reserved = 0;
-    }
+    smp.fold(h.done ? h.n_iter - 1 : max_iter);
+    finish_solve(c, h, max_iter, info);
+    const int n_it = c.last_cg_iters;
     // what mistark_dist_fused_bench replays: S_n, R_n and V_{n+1} of a converged solve found the messages M1_n / M2_n complete, and nobody has
     // pushed behind them
     c.fused_replay.valid = h.done && h.converged && !h.indef && n_it >= 1;
@@ -2282,7 +2285,6 @@ void fused_pcg_replay(Context& c, int n_launches, double* s_us, double* v_us)
     if (v_us) *v_us = 1e3 * ms[1] / n_launches;
 }
 
-static double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // ---- option "cg_variant" = 1 on ONE GPU: the Chronopoulos-Gear iteration of the sharded solve without the windows -----------------------------
 // Two launches per iteration instead of three: S (the solver's SpMV on u = M^-1 r, partial w.u) and V (k_cg_vec in its local mode: every
 // workgroup re-reduces the partial sums, decides, updates p, s, x, r, u). Same iterates in exact arithmetic; p.Ap is delta - beta gamma /
@@ -2299,24 +2301,13 @@ static void pcg_cg(Context& c, const double* rhs_dev, double abs_tol, double rel
     if (c.perm_active) c.xl.ensure((size_t)c.ndofs);
     double* const xs = c.perm_active ? c.xl.p : c.du.p;
     double *u = c.z.p, *w = c.q.p, *p = c.p.p, *s = c.p2.p, *r = c.r.p;
-    {
-        // prologue as in pcg(): preconditioner, x = 0, r = b, u = M^-1 r; partial (r.r, r.u) where V_1 expects those of "V_0" (parity 0)
-        const BsrPart& d1 = c.part[1];
-        hipLaunchKernelGGL(k_pcg_prologue, dim3(gv), dim3(BLOCK), 0, c.stream, rhs_dev, rhs_scale, (const float*)c.part[0].vals.p, (const int32_t*)c.diag_slot[0].p,
-                           d1.nnzb ? (const float*)d1.vals.p : (const float*)nullptr, (const int32_t*)c.diag_slot[1].p, c.nbr, c.dinv.p, xs, r, u, p, pr[0][1], pr[0][0],
-                           c.perm_active ? (const int32_t*)c.iperm.p : (const int32_t*)nullptr);
-        hipLaunchKernelGGL(k_pcg_init2, dim3(1), dim3(BLOCK), 0, c.stream, pr[0][1], pr[0][0], gv, abs_tol, c.ctrl.p, 1);
-    }
+    // preconditioner, x = 0, r = b, u = M^-1 r; partial (r.r, r.u) where V_1 expects those of "V_0" (parity 0)
+    launch_prologue(c, rhs_dev, rhs_scale, gv, abs_tol, xs, r, u, p, pr[0][1], pr[0][0]);
     constexpr int BATCH = 4;
-    PcgCtrl* hs[2] = {reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048), reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048 + 64)};
-    const int epoch = ++c.pcg_epoch;
     int k = 1;
     bool tail_done = false;
     CgFast f{};
-    auto launch_batch = [&](int slot) {
-        hs[slot]->epoch = epoch - 1;
-        hs[slot]->done = 0;
-        hs[slot]->n_iter = -1;
+    auto launch_batch = [&](int, PcgCtrl* host_slot, int epoch) {
         const int k_end = std::min(max_iter + 1, k + BATCH - 1);
         for (; k <= k_end; k++) {
             const bool check_only = k == max_iter + 1;
@@ -2324,60 +2315,15 @@ static void pcg_cg(Context& c, const double* rhs_dev, double abs_tol, double rel
             hipLaunchKernelGGL(k_cg_vec, dim3(gv), dim3(BLOCK), 0, c.stream, k, check_only ? 1 : 0, stop_on_indef, abs_tol, rel_tol, f, 0u, 0u, (const float*)c.dinv.p, c.nbr, u,
                                (const double*)w, p, s, xs, r, c.ctrl.p, dyn ? (const int32_t*)m1.crow_of_row.p : (const int32_t*)nullptr, (const uint32_t*)m1.row_chunk0.p,
                                (const double*)m1.yd.p, (const double*)m1.chunk_partial.p, (const int32_t*)nullptr, (const uint32_t*)nullptr, pr[k & 1][0], pr[k & 1][1],
-                               k == k_end ? hs[slot] : (PcgCtrl*)nullptr, epoch, 0, (const double*)part_wu, gs, (const double*)pr[(k - 1) & 1][0], (const double*)pr[(k - 1) & 1][1], gv, 0);
+                               k == k_end ? host_slot : (PcgCtrl*)nullptr, epoch, 0, (const double*)part_wu, gs, (const double*)pr[(k - 1) & 1][0], (const double*)pr[(k - 1) & 1][1], gv, 0);
             if (check_only) tail_done = true;
         }
         return k_end;
     };
-    PcgCtrl h{};
-    int slot = 0;
-    int k_end_cur = launch_batch(0);
-    for (;;) {
-        const bool more = !tail_done;
-        int k_end_next = 0;
-        if (more) k_end_next = launch_batch(slot ^ 1);
-        const volatile PcgCtrl* v = hs[slot];
-        const double t_wait = now_seconds();
-        auto reported = [&] { return v->epoch == epoch && (v->done || v->n_iter >= k_end_cur); };
-        for (uint64_t spins = 0; !reported(); spins++) {
-            __builtin_ia32_pause();
-            if ((spins & 0xfffff) != 0xfffff) continue;
-            const hipError_t q = hipStreamQuery(c.stream);
-            if (q != hipErrorNotReady) {
-                MS_CHECK(q);
-                if (!reported()) {
-                    PcgCtrl dev{};
-                    MS_CHECK(hipMemcpy(&dev, c.ctrl.p, sizeof(PcgCtrl), hipMemcpyDeviceToHost));
-                    hs[slot]->converged = dev.converged;
-                    hs[slot]->indef = dev.indef;
-                    hs[slot]->error = dev.error;
-                    hs[slot]->n_iter = dev.done ? dev.n_iter : k_end_cur;
-                    hs[slot]->done = dev.done ? 1 : 0;
-                    hs[slot]->epoch = epoch;
-                }
-                break;
-            }
-            if (now_seconds() - t_wait > 60.0) throw Error("pcg: the device did not report iteration " + std::to_string(k_end_cur) + " within 60 s");
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        h = *hs[slot];
-        if (h.done || !more) break;
-        slot ^= 1;
-        k_end_cur = k_end_next;
-    }
+    const PcgCtrl h = run_batches(c, 60.0, "pcg: the device did not report iteration", launch_batch, [&] { return !tail_done; }, [](int, const PcgCtrl&, int) {});
     if (c.perm_active) rows_from_solver(c, xs, c.du.p);
-    const int n_it = h.done ? h.n_iter : max_iter;
-    c.last_cg_iters = n_it;
-    if (info) {
-        info->converged = h.done ? h.converged : 0;
-        info->n_iterations = n_it;
-        info->found_indefiniteness = h.indef;
-        info->error = h.error;
-        info->reserved = 0;
-    }
+    finish_solve(c, h, max_iter, info);
 }
-// SpMV timing inside the solver: every SPMV_SAMPLE-th launch is bracketed by a pair of pooled HIP events on the engine's stream
-constexpr int SPMV_SAMPLE = 32;  // (a sampled launch costs the stream ~14 us of marker packets: 1.3 % of the timed region at every 16th launch, measured)
 void pcg(Context& c, const double* rhs_dev, double abs_tol, double rel_tol, int max_iter, int stop_on_indef, mistark_pcg_info* info, double rhs_scale)
 {
     if (!c.have_matrix) throw Error("pcg: matrix not assembled");
@@ -2405,147 +2351,36 @@ void pcg(Context& c, const double* rhs_dev, double abs_tol, double rel_tol, int 
     // (solver numbering: the solution accumulates in a scratch vector and is written to c.du in the caller's numbering at the end)
     if (c.perm_active) c.xl.ensure((size_t)c.ndofs);
     double* const xs = c.perm_active ? c.xl.p : c.du.p;
-    {
-        const BsrPart& d1 = c.part[1];
-        hipLaunchKernelGGL(k_pcg_prologue, dim3(gv), dim3(BLOCK), 0, c.stream, rhs_dev, rhs_scale, (const float*)c.part[0].vals.p, (const int32_t*)c.diag_slot[0].p,
-                           d1.nnzb ? (const float*)d1.vals.p : (const float*)nullptr, (const int32_t*)c.diag_slot[1].p, c.nbr, c.dinv.p, xs, c.r.p, c.z.p, c.p.p,
-                           part_bb, part_rz, c.perm_active ? (const int32_t*)c.iperm.p : (const int32_t*)nullptr);
-    }
-    hipLaunchKernelGGL(k_pcg_init2, dim3(1), dim3(BLOCK), 0, c.stream, part_bb, part_rz, gv, abs_tol, c.ctrl.p, 1);
-    // Iterations are launched in batches of PCG_BATCH; the last iteration of a batch writes the control block to a pinned slot.
-    // The host launches batch b+1 BEFORE it waits for batch b's slot, so the GPU never idles on the host's
-    // convergence check, and at most one batch of device-side no-op launches (ctrl->done) is wasted after convergence.
+    launch_prologue(c, rhs_dev, rhs_scale, gv, abs_tol, xs, c.r.p, c.z.p, c.p.p, part_bb, part_rz);
+    // iterations in batches of PCG_BATCH with one look-ahead batch in flight (run_batches)
     constexpr int PCG_BATCH_MAX = 8;  // (sizes of the sampling buffers)
     // (option "pcg_batch"; 0 = by size: 3 for the large systems, whose iterations are long enough for the host to keep up with shorter batches and
     // whose solves then queue fewer no-op launches behind the iteration that converged — configs[3]: 1.140 against 1.155 ms per solve, 2 / 3 / 4 / 6
     // = 1.145 / 1.140 / 1.155 / 1.176 —, 4 for the small ones, whose 13 us iterations the host barely outruns: configs[0] 254 against 244-248)
     const int PCG_BATCH = std::min(std::max(c.pcg_batch > 0 ? c.pcg_batch : (c.nbr >= 100000 ? 3 : 4), 1), PCG_BATCH_MAX);
-    PcgCtrl* hs[2] = {reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048), reinterpret_cast<PcgCtrl*>(host_scratch(c, 4096) + 2048 + 64)};  // pinned
-    const int epoch = ++c.pcg_epoch;
-    std::vector<int> sampled[2];
-    int clk_grid[2] = {0, 0};
+    SpmvSampler smp[2] = {{c, c.spmv_clk, (size_t)2 * PCG_BATCH_MAX, 0, true}, {c, c.spmv_clk, (size_t)2 * PCG_BATCH_MAX, (size_t)PCG_BATCH_MAX, true}};  // per slot
     int k = 1;
-    auto launch_batch = [&](int slot) {
+    auto launch_batch = [&](int slot, PcgCtrl* host_slot, int epoch) {
         const int k_end = std::min(max_iter, k + PCG_BATCH - 1);
-        // (the slot is written by the batch's last direction kernel; the host waits for it by watching the slot itself — an event record
-        // between batches is a marker packet the next SpMV waits behind: 5 us per batch)
-        hs[slot]->epoch = epoch - 1;  // (whatever a straggler of the previous solve writes here carries the previous epoch, too)
-        hs[slot]->done = 0;
-        hs[slot]->n_iter = -1;
-        sampled[slot].clear();
+        smp[slot].clear();
         for (; k <= k_end; k++) {
             const bool sample = c.time_spmv && (k % SPMV_SAMPLE) == 0;
-            const size_t e0 = (size_t)slot * 3 * PCG_BATCH_MAX + 3 * sampled[slot].size();
-            if (sample) {
-                while (c.ev.size() < (size_t)6 * PCG_BATCH_MAX) {
-                    hipEvent_t e;
-                    MS_CHECK(hipEventCreate(&e));
-                    c.ev.push_back(e);
-                }
-                MS_CHECK(hipEventRecord(c.ev[e0], c.stream));
-            }
-            uint64_t* clk = nullptr;
-            if (sample) {
-                if (!c.spmv_clk) MS_CHECK(hipHostMalloc((void**)&c.spmv_clk, sizeof(uint64_t) * 2 * PCG_BATCH_MAX * 2 * MAX_PARTIALS, hipHostMallocDefault));
-                clk = c.spmv_clk + ((size_t)slot * PCG_BATCH_MAX + sampled[slot].size()) * 2 * MAX_PARTIALS;
-                std::memset(clk, 0, sizeof(uint64_t) * 2 * MAX_PARTIALS);
-            }
-            const int gs = launch_spmv<0>(c, c.p.p, c.q.p, c.p.p, part_pq, c.ctrl.p, /*combine=*/false, clk);
-            if (sample) {
-                clk_grid[slot] = gs;
-                MS_CHECK(hipEventRecord(c.ev[e0 + 1], c.stream));
-                // an empty bracket right behind: what a pair of event records costs the stream by itself (the marker packets' own processing
-                // is inside every bracketed duration; bench.py reports both figures)
-                MS_CHECK(hipEventRecord(c.ev[e0 + 2], c.stream));
-                sampled[slot].push_back(k);
-            }
+            const int gs = launch_spmv<0>(c, c.p.p, c.q.p, c.p.p, part_pq, c.ctrl.p, /*combine=*/false, sample ? smp[slot].begin(k) : nullptr);
+            if (sample) smp[slot].end(gs);
             hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(BLOCK), 0, c.stream, k, stop_on_indef, part_pq, gs, c.dinv.p, c.nbr, (const double*)c.p.p, c.q.p, xs, c.r.p, c.z.p, part_rr,
                                part_rz, c.ctrl.p, dyn ? (const int32_t*)m1.crow_of_row.p : nullptr, (const uint32_t*)m1.row_chunk0.p, (const double*)m1.yd.p,
                                (const double*)m1.chunk_partial.p);
             hipLaunchKernelGGL(k_pcg_dir, dim3(gv), dim3(BLOCK), 0, c.stream, k, abs_tol, rel_tol, part_rr, part_rz, gv, c.ndofs, c.z.p, c.p.p, c.ctrl.p, 1,
-                               k == k_end ? hs[slot] : (PcgCtrl*)nullptr, epoch);
+                               k == k_end ? host_slot : (PcgCtrl*)nullptr, epoch);
         }
         // the control block reaches the pinned slot from the batch's last k_pcg_dir itself (round 1: a copy command on another engine, 4 us
         // + a 5.6 us gap; then a one-wavefront copy kernel, 4 us + its boundary, every four iterations)
         return k_end;
     };
-    auto drain = [&](int slot, int last_real_iter) {
-        for (size_t i = 0; i < sampled[slot].size(); i++) {
-            if (sampled[slot][i] > last_real_iter) continue;  // early-exit launch after convergence
-            float ms = 0.f;
-            const size_t e0 = (size_t)slot * 3 * PCG_BATCH_MAX + 3 * i;
-            float ms_empty = 0.f;
-            if (hipEventElapsedTime(&ms, c.ev[e0], c.ev[e0 + 1]) == hipSuccess && hipEventElapsedTime(&ms_empty, c.ev[e0 + 1], c.ev[e0 + 2]) == hipSuccess) {
-                c.spmv_ms_sum += ms;
-                c.spmv_empty_ms_sum += ms_empty;
-                c.spmv_n++;
-            }
-            if (c.spmv_clk && clk_grid[slot] > 0) {  // the same launch on the device clock
-                const uint64_t* clk = c.spmv_clk + ((size_t)slot * PCG_BATCH_MAX + i) * 2 * MAX_PARTIALS;
-                uint64_t t0 = ~0ull, t1 = 0;
-                bool complete = true;
-                for (int b = 0; b < clk_grid[slot]; b++) {
-                    if (clk[2 * b] == 0 || clk[2 * b + 1] == 0) { complete = false; break; }
-                    t0 = std::min(t0, clk[2 * b]);
-                    t1 = std::max(t1, clk[2 * b + 1]);
-                }
-                if (complete && t1 > t0) {
-                    c.spmv_clk_ticks += (double)(t1 - t0);
-                    c.spmv_clk_n++;
-                }
-            }
-        }
-    };
-    PcgCtrl* h = nullptr;
-    int slot = 0;
-    int k_end_cur = launch_batch(0);
-    for (;;) {
-        const bool more = k <= max_iter;
-        const int k_end_next = more ? launch_batch(slot ^ 1) : 0;  // keep the GPU fed while the host looks at the previous batch
-        const volatile PcgCtrl* v = hs[slot];
-        const double t_wait = now_seconds();
-        auto reported = [&] { return v->epoch == epoch && (v->done || v->n_iter >= k_end_cur); };
-        for (uint64_t spins = 0; !reported(); spins++) {
-            __builtin_ia32_pause();
-            if ((spins & 0xfffff) != 0xfffff) continue;
-            // now and then a real look at the stream, as publish() does: a failed launch surfaces as its error, and a stream that has
-            // drained without the slot being written (host memory the device's writes do not reach while kernels run) is answered from
-            // the device's own control block instead of a time-out
-            const hipError_t q = hipStreamQuery(c.stream);
-            if (q != hipErrorNotReady) {
-                MS_CHECK(q);
-                if (!reported()) {
-                    PcgCtrl dev{};
-                    MS_CHECK(hipMemcpy(&dev, c.ctrl.p, sizeof(PcgCtrl), hipMemcpyDeviceToHost));
-                    hs[slot]->converged = dev.converged;
-                    hs[slot]->indef = dev.indef;
-                    hs[slot]->error = dev.error;
-                    hs[slot]->n_iter = dev.done ? dev.n_iter : k_end_cur;
-                    hs[slot]->done = dev.done ? 1 : 0;
-                    hs[slot]->epoch = epoch;
-                }
-                break;
-            }
-            if (now_seconds() - t_wait > 60.0) throw Error("pcg: the device did not report batch " + std::to_string(k_end_cur) + " within 60 s");
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        h = hs[slot];
-        if (c.time_spmv) drain(slot, h->done ? h->n_iter : k_end_cur);
-        if (h->done || !more) break;
-        slot ^= 1;
-        k_end_cur = k_end_next;
-    }
-    // (a look-ahead batch launched after convergence consists of device-side no-ops; later work queues behind it on the same stream)
+    const PcgCtrl h = run_batches(c, 60.0, "pcg: the device did not report batch", launch_batch, [&] { return k <= max_iter; },
+                                  [&](int slot, const PcgCtrl& b, int k_end) { smp[slot].fold(b.done ? b.n_iter : k_end); });
     if (c.perm_active) rows_from_solver(c, xs, c.du.p);
-    const int n_it = h->done ? h->n_iter : max_iter;
-    c.last_cg_iters = n_it;
-    if (info) {
-        info->converged = h->done ? h->converged : 0;
-        info->n_iterations = n_it;
-        info->found_indefiniteness = h->indef;
-        info->error = h->error;
-        info->reserved = 0;
-    }
+    finish_solve(c, h, max_iter, info);
 }
 
 Context::~Context()
