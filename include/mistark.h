@@ -145,6 +145,24 @@ int mistark_eval(mistark_ctx* ctx, int mode, double* E, double* grad_host);
 int mistark_get_element_hessians(mistark_ctx* ctx, int potential, double* values, int32_t* block_rows, int32_t* nb_out);
 int mistark_get_element_energies(mistark_ctx* ctx, int potential, double* values);
 
+/* ---- force readout --------------------------------------------------------------------------------------------------------
+ * The generalised force of a set S of potentials at the current DoFs u: f = -scale * sum over S of dE_P/du (with STARK's velocity DoFs,
+ * x1 = x0 + dt v1, scale = 1/dt gives Newtons). A pipeline of its own beside mistark_eval: every selected potential is evaluated through its generic
+ * hyper-dual expression, node gradients go to a pool of the readout's own, are sorted by block row (stable) and summed row by row in that order.
+ * No floating-point atomics: two readouts of one state give the same bits. Nothing mistark_eval, the matrix or the contact detector own is written;
+ * contact and friction tables are read as installed (no search runs). May be called between solves and from any Newton callback. Refused: sharded
+ * contexts (single-rank accessor), user-defined potentials (mistark_potential_custom) in the set, registration-only contexts. */
+/* Node forces of every element of one potential at the current DoFs: out[e][k][3] = -scale * dE_e/du_(block k), e < n_elem, k < NB
+ * (zeros for elements whose condition is off); block_rows[e][k] as mistark_get_element_hessians reports them. Pointers nullable
+ * (query sizes with both NULL). */
+int mistark_potential_element_forces(mistark_ctx* ctx, int potential, double scale, double* out, int32_t* block_rows, int64_t* n_elem, int32_t* nb);
+/* f_host[ndofs] = -scale * sum over the listed potentials of dE/du, rows summed in a fixed order (bit-reproducible). n = 0: all potentials. */
+int mistark_forces(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double scale, double* f_host);
+/* Resultant of the same forces over `rows` (block rows, list order): out[0..3) = sum f; out[3..6) = sum (pos_r - about) x f_r when
+ * pos_host (3 doubles per listed row) is given, else 0. */
+int mistark_forces_resultant(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double scale, const int32_t* rows, int64_t n_rows,
+                             const double* pos_host, const double about[3], double out[6]);
+
 /* ---- projection + assembly ------------------------------------------------------------------------------------------ */
 /* ElementHessians::project_to_PD_inplace__all / project_to_PD_for_update__selectively (ElementHessians.cpp:48-67,79-182;
  * project_to_PD.cpp:12-32). active_blocks: NULL = all elements, else ndofs/3 flags; only not-yet-projected elements
@@ -354,7 +372,8 @@ int mistark_sync(mistark_ctx* ctx);
  * "asm_short_slots_P" / "asm_long_slots_P" / "asm_vlong_slots_P" (P = 0 static, 1 dynamic matrix part: BSR blocks of the current pattern summed by
  * the one-lane / one-wavefront / 64-wavefront gather kernel, by the length of their contribution lists), "llt_path" / "llt_panel_rows" /
  * "llt_panels" / "llt_fronts" (the last DirectLLT solve: 0 dense, 1 band, 2 multifrontal, -1 none yet; block rows per panel — multifrontal: of the
- * largest front —, panels, fronts). */
+ * largest front —, panels, fronts), "force_readouts" (force readout calls that launched) / "force_long_rows" (block rows of the last readout
+ * that were summed by a whole wavefront: more than 256 contributions). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

@@ -210,6 +210,16 @@ int mistark_sim_get_info(mistark_sim* sim, mistark_sim_info* info);
 int mistark_sim_get_points(mistark_sim* sim, int which, double* out);
 /* writes x0 / v0 (which: 1, 2) from the caller's buffer and uploads the state */
 int mistark_sim_set_points(mistark_sim* sim, int which, const double* in);
+/* Force recording (off by default; not in the reference). After run_one_step the state has advanced (x0 <- x1), so a readout taken by the caller
+ * afterwards would evaluate another state: recording happens inside the step, after a successful Newton solve and before the step is accepted.
+ * `groups`: comma-separated prefixes of potential names, one group per entry ("contact_,friction_,EnergyTetStrain"); an empty string is the one
+ * group of all potentials; NULL switches recording off. Per group the engine's force readout (mistark.h: mistark_forces) runs with
+ * scale = 1 / dt — Newtons — and the nodal vector stays on the device. With recording off nothing is registered, launched or allocated. */
+int mistark_sim_record_forces(mistark_sim* sim, const char* groups);
+/* The vectors of the last accepted step, group by index: points_out [n_points x 3], rb_out [n_rigid_bodies x 6] = (force, torque) per body: its rows
+ * of the DoF sets v1 and w1 (nullable outputs). The torque is the generalised force conjugate to w1 * dt; it equals the physical torque to first
+ * order in |w1| * dt (the rotation of a step is integrated from w1 through a quaternion update, not linearly). */
+int mistark_sim_get_forces(mistark_sim* sim, int group, double* points_out, double* rb_out);
 /* The part of a time step before the Newton solve (Stark.cpp:145-156: before_time_step callbacks = friction tables at the start-of-step
  * geometry, rigid-body caches, v1 = 0) and the Newton callback that precedes every evaluation (contact tables at the current DoFs), as
  * separate calls: what the reference's harness does to take a stage snapshot at a given state (callbacks->run_before_time_step();

@@ -8,6 +8,7 @@
 
 #include "dist.hpp"
 #include "engine.hpp"
+#include "forces.hpp"
 
 using namespace mistark;
 
@@ -574,6 +575,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "asm_short_slots_0" || n == "asm_short_slots_1") { ensure_pattern(c); const BsrPart& m = c.part[n.back() - '0']; *out = m.nnzb - m.n_long - m.n_vlong; }
     else if (n == "asm_long_slots_0" || n == "asm_long_slots_1") { ensure_pattern(c); *out = c.part[n.back() - '0'].n_long; }
     else if (n == "asm_vlong_slots_0" || n == "asm_vlong_slots_1") { ensure_pattern(c); *out = c.part[n.back() - '0'].n_vlong; }
+    else if (n == "force_readouts") *out = c.n_force_readouts;
+    else if (n == "force_long_rows") *out = force_long_rows(c);
     else if (n == "llt_path") *out = c.llt_last_path;
     else if (n == "llt_panel_rows") *out = c.llt_last_panel_rows;
     else if (n == "llt_panels") *out = c.llt_last_panels;
@@ -690,6 +693,27 @@ int mistark_get_element_energies(mistark_ctx* ctx, int potential, double* values
         MS_CHECK(hipMemcpyAsync(values, c.elemE.p + P.e_off, (size_t)P.n_elem * sizeof(double), hipMemcpyDeviceToHost, c.stream));
         MS_CHECK(hipStreamSynchronize(c.stream));
     }
+    API_END(0)
+}
+
+// ---- force readout (forces.hip) ----------------------------------------------------------------------------------------
+int mistark_potential_element_forces(mistark_ctx* ctx, int potential, double scale, double* out, int32_t* block_rows, int64_t* n_elem, int32_t* nb)
+{
+    API_BEGIN
+    force_elements_host(ctx->c, potential, scale, out, block_rows, n_elem, nb);
+    API_END(0)
+}
+int mistark_forces(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double scale, double* f_host)
+{
+    API_BEGIN
+    force_nodal_host(ctx->c, potentials, n, scale, f_host);
+    API_END(0)
+}
+int mistark_forces_resultant(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double scale, const int32_t* rows, int64_t n_rows, const double* pos_host, const double about[3],
+                             double out[6])
+{
+    API_BEGIN
+    force_resultant_host(ctx->c, potentials, n, scale, rows, n_rows, pos_host, about, out);
     API_END(0)
 }
 
@@ -1337,3 +1361,27 @@ int mistark_spmv_timing(mistark_ctx* ctx, int reset, double* avg_ms, int64_t* n,
 }
 
 }  // extern "C"
+
+// forces.hpp: the host mirror's side of the force readout
+namespace mistark {
+int force_potentials_by_prefix(mistark_ctx* ctx, const std::string& prefix, std::vector<int32_t>& out)
+{
+    API_BEGIN
+    out.clear();
+    for (size_t p = 0; p < ctx->c.pots.size(); p++)
+        if (ctx->c.pots[p].name.compare(0, prefix.size(), prefix) == 0) out.push_back((int32_t)p);
+    API_END(0)
+}
+int force_record(mistark_ctx* ctx, int slot, const std::vector<int32_t>& pots, double scale)
+{
+    API_BEGIN
+    force_record_slot(ctx->c, slot, pots.data(), (int32_t)pots.size(), false, scale);
+    API_END(0)
+}
+int force_fetch(mistark_ctx* ctx, int slot, double* f_host, int64_t ndofs)
+{
+    API_BEGIN
+    force_fetch_slot(ctx->c, slot, f_host, ndofs);
+    API_END(0)
+}
+}  // namespace mistark

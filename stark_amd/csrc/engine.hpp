@@ -520,6 +520,25 @@ struct Context
     DevBuf<unsigned char> src_ranges;  // descriptor table of k_make_desc
     struct ContactSystem* contact = nullptr;  // device contact detector (contact.hip), created by mistark_contact_init
 
+    // Force readout (forces.hip): a pipeline beside eval() with buffers of its own — the evaluation's gradient, pools and element data, the matrix and
+    // the detector's lists are never written. Node gradients of the selected potentials -> fr_pool, contributions sorted by block row, one
+    // segmented sum in sorted order -> a nodal vector (fr_out, or a slot kept on the device for the host mirror).
+    DevBuf<double> fr_pool, fr_elemE, fr_out, fr_res, fr_pos;
+    DevBuf<uint32_t> fr_key, fr_key_alt, fr_val, fr_val_alt;
+    DevBuf<uint32_t> fr_stat;        // [0]: rows of the last readout summed by a whole wavefront (counter "force_long_rows")
+    DevBuf<int32_t> fr_rows;
+    DevBuf<unsigned char> fr_desc;
+    DevBuf<uint8_t> fr_cub_tmp;
+    struct ForceSlot
+    {
+        DevBuf<double> f;
+        int64_t n = -1;              // scalars recorded (-1: nothing yet)
+        bool zero = false;           // nothing contributed: no launch, the vector is zero
+    };
+    std::vector<ForceSlot> force_slots;
+    int64_t n_force_readouts = 0;   // counter "force_readouts": readout calls that launched
+    bool fr_stat_valid = false;
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -605,6 +624,18 @@ double reduce_dot(Context& c, const double* a, const double* b, int64_t n);
 void vec_axpby(Context& c, double* dst, double a, const double* x, double b, const double* y, int64_t n);
 void vec_fill(Context& c, double* dst, double v, int64_t n);
 void vec_neg(Context& c, double* dst, const double* x, int64_t n);
+// Force readout. kernels.hip: the generic hyper-dual kernel of P's kind with its node gradients redirected to `pool` ([block][element][3], no
+// atomics, zeros for elements switched off) and its element energies to `scratchE`; on c.stream.
+void launch_force_elements(Context& c, const Potential& P, double* pool, double* scratchE);
+// forces.hip: f_dev[ndofs] = -scale * sum over the listed potentials of dE/du (all = every potential); returns false when nothing contributed
+// (no launch, f_dev untouched: the vector is zero)
+bool force_readout(Context& c, const int32_t* pots, int32_t n, bool all, double scale, double* f_dev);
+void force_elements_host(Context& c, int pot, double scale, double* out, int32_t* block_rows, int64_t* n_elem, int32_t* nb);
+void force_nodal_host(Context& c, const int32_t* pots, int32_t n, double scale, double* f_host);
+void force_resultant_host(Context& c, const int32_t* pots, int32_t n, double scale, const int32_t* rows, int64_t n_rows, const double* pos_host, const double* about, double* out);
+int64_t force_long_rows(Context& c);  // counter "force_long_rows"
+void force_record_slot(Context& c, int slot, const int32_t* pots, int32_t n, bool all, double scale);
+void force_fetch_slot(Context& c, int slot, double* f_host, int64_t n);
 int find_kind(const char* name);
 int kind_nb(int kind);
 int kind_nbind(int kind);

@@ -66,8 +66,9 @@ Vec3 RigidBodyDynamics::get_d1(int b, const Vec3& d_loc, double dt) const { retu
 void RigidBodyDynamics::register_dofs(mistark_ctx* ctx)
 {
     const int64_t n = get_n_bodies();
-    stark.check(mistark_add_dof_set(ctx, "rigid.v1", n ? v1[0].data() : nullptr, 3 * n));
-    stark.check(mistark_add_dof_set(ctx, "rigid.w1", n ? w1[0].data() : nullptr, 3 * n));
+    stark.check(stark.force_set_rb_v = mistark_add_dof_set(ctx, "rigid.v1", n ? v1[0].data() : nullptr, 3 * n));
+    stark.check(stark.force_set_rb_w = mistark_add_dof_set(ctx, "rigid.w1", n ? w1[0].data() : nullptr, 3 * n));
+    stark.force_n_rb = n;
     id_v1 = id_w1 = id_v0 = id_w0 = id_a = id_aa = id_force = id_torque = id_t0 = id_q0_ = -1;
     if (n == 0) return;
     stark.check(id_v1 = mistark_array(ctx, v1[0].data(), n, 3));

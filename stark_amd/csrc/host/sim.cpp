@@ -1,6 +1,7 @@
 // host/sim.cpp — see sim.hpp. Reference citations are given per function.
 #include "sim.hpp"
 #include "bind.hpp"
+#include "../forces.hpp"
 
 #include <limits>
 #include <chrono>
@@ -50,6 +51,9 @@ void Stark::ensure_registered()
         else if (ex.rccl_unique_id.size() == 128) check(mistark_dist_init_rccl(ctx, ex.rank, ex.world, ex.rccl_unique_id.data()));
         else throw std::runtime_error("multi-GPU run without a communicator id");
     }
+    force_set_points = force_set_rb_v = force_set_rb_w = -1;
+    force_n_points = force_n_rb = 0;
+    forces_recorded = false;  // (recorded vectors live in the context just replaced)
     for (auto* m : models) m->register_dofs(ctx);
     dt_array_id = mistark_array(ctx, &dt, 1, 1);
     check(dt_array_id);
@@ -175,6 +179,17 @@ bool Stark::run_one_step()
     total_evaluations += st.n_evaluations;
 
     if (result == MISTARK_SUCCESSFUL) {
+        if (force_recording) {
+            // the callbacks that precede an evaluation, as the engine's own evaluations have them: at an unchanged state they are answered from the
+            // installed tables
+            for (auto& f : n.before_energy_evaluation) f();
+            std::vector<int32_t> pots;
+            for (size_t g = 0; g < force_groups.size(); g++) {
+                check(force_potentials_by_prefix(ctx, force_groups[g], pots));
+                check(force_record(ctx, (int)g, pots, 1.0 / dt));
+            }
+            forces_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -198,6 +213,46 @@ bool Stark::run_one_step()
     dt /= 2.0;
     if (dt < settings.simulation.time_step_size_lower_bound) return false;
     return true;
+}
+void Stark::record_forces(const char* groups)
+{
+    force_groups.clear();
+    force_recording = groups != nullptr;
+    forces_recorded = false;
+    if (!groups) return;
+    std::string cur;
+    for (const char* p = groups;; p++) {
+        if (*p == ',' || *p == 0) {
+            force_groups.push_back(cur);
+            cur.clear();
+            if (*p == 0) break;
+        } else {
+            cur.push_back(*p);
+        }
+    }
+}
+void Stark::get_forces(int group, double* points_out, double* rb_out)
+{
+    if (!force_recording) throw std::runtime_error("get_forces: force recording is off (record_forces)");
+    if (group < 0 || group >= (int)force_groups.size()) throw std::runtime_error("get_forces: no group " + std::to_string(group));
+    if (!ctx || !forces_recorded) throw std::runtime_error("get_forces: no time step has been accepted since recording was switched on");
+    const int64_t ndofs = mistark_ndofs(ctx);
+    std::vector<double> f((size_t)ndofs);
+    check(force_fetch(ctx, group, f.data(), ndofs));
+    if (points_out && force_n_points > 0) {
+        const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
+        if (r0 < 0) throw std::runtime_error("get_forces: the point set has no DoFs");
+        std::copy(f.begin() + 3 * r0, f.begin() + 3 * (r0 + force_n_points), points_out);
+    }
+    if (rb_out && force_n_rb > 0) {
+        const int64_t rv = mistark_dof_set_first_row(ctx, force_set_rb_v), rw = mistark_dof_set_first_row(ctx, force_set_rb_w);
+        if (rv < 0 || rw < 0) throw std::runtime_error("get_forces: the rigid bodies have no DoFs");
+        for (int64_t b = 0; b < force_n_rb; b++)
+            for (int d = 0; d < 3; d++) {
+                rb_out[6 * b + d] = f[(size_t)(3 * (rv + b) + d)];
+                rb_out[6 * b + 3 + d] = f[(size_t)(3 * (rw + b) + d)];
+            }
+    }
 }
 std::string Stark::get_frame_path(const std::string& name) const
 {
@@ -307,6 +362,8 @@ void PointDynamics::register_dofs(mistark_ctx* ctx)
     const int64_t n = (int64_t)size();
     dof_set = mistark_add_dof_set(ctx, "soft.v1", n ? v1[0].data() : nullptr, 3 * n);
     stark.check(dof_set);
+    stark.force_set_points = dof_set;
+    stark.force_n_points = n;
     if (n == 0) return;
     stark.check(id_v1 = mistark_array(ctx, v1[0].data(), n, 3));
     stark.check(id_X = mistark_array(ctx, X[0].data(), n, 3));

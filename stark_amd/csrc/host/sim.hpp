@@ -138,6 +138,14 @@ public:
     int gravity_array() const { return gravity_array_id; }
     void ensure_registered();  // (re)register every model with the engine if anything changed
     void check(int rc) const;  // throws std::runtime_error with mistark_last_error on rc < 0
+    // Force recording (opt-in, not in the reference): after a successful Newton solve and before on_time_step_accepted — the state then still is the
+    // one the solve converged at — the engine's force readout runs once per group of potentials (name prefixes) with scale = 1 / dt; the nodal
+    // vectors stay on the device until get_forces() downloads one. Off: nothing is registered, launched or allocated.
+    void record_forces(const char* groups);  // comma-separated name prefixes, one group per entry ("" = all potentials); nullptr: off
+    void get_forces(int group, double* points_out /* n_points x 3, nullable */, double* rb_out /* n_rb x 6: force, torque; nullable */);
+    // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
+    int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
+    int64_t force_n_points = 0, force_n_rb = 0;
 
 private:
     std::vector<Registrable*> models;
@@ -145,6 +153,9 @@ private:
     bool registration_dirty = true;
     int dt_array_id = -1, gravity_array_id = -1;
     double dt_uploaded = -1.0;
+    bool force_recording = false;
+    std::vector<std::string> force_groups;
+    bool forces_recorded = false;  // ... in the current engine context
     void _initialize();
     void _write_frame();
 };

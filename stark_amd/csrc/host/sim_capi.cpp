@@ -737,6 +737,18 @@ int mistark_sim_run_one_step(mistark_sim* s)
     _ret = s->sim->get_stark().run_one_step() ? 1 : 0;
     SIM_END
 }
+int mistark_sim_record_forces(mistark_sim* s, const char* groups)
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_forces(groups);
+    SIM_END
+}
+int mistark_sim_get_forces(mistark_sim* s, int group, double* points_out, double* rb_out)
+{
+    SIM_BEGIN
+    s->sim->get_stark().get_forces(group, points_out, rb_out);
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

@@ -885,6 +885,31 @@ static void launch_eval(Context& c, Potential& P, int mode)
     if (mode != MISTARK_EVAL_P) launch_grad_gather(c, P);
 }
 
+// Force readout (forces.hip): the generic kernel on a copy of the potential's argument block — node gradients to the readout pool (which also
+// bypasses the hot rows), element energies to a scratch array, no gradient vector. Nothing eval() owns is written.
+template <class En>
+static void launch_force_kind(Context& c, const Potential& P, double* pool, double* scratchE)
+{
+    constexpr int n = 3 * En::NB, NP = n * (n + 1) / 2;
+    PotArgs A = P.args;
+    A.gpool = pool;
+    A.n_gpool = P.n_elem;
+    hipLaunchKernelGGL((k_eval_pgh<En, false>), dim3(grid_for((int64_t)A.e_count * NP)), dim3(BLOCK), 0, c.stream, A, scratchE, (double*)nullptr, (double*)nullptr);
+}
+void launch_force_elements(Context& c, const Potential& P, double* pool, double* scratchE)
+{
+    if (P.kind == KIND_CUSTOM) throw Error("force readout: potential '" + P.name + "' is user-defined (its kernels have no pool path)");
+    if (P.args.e_count == 0) return;
+    if (P.args.elem_list || P.args.e_count != P.n_elem) throw Error("force readout: single-rank accessor");
+    int k = 0;
+#define X(En)                                                            \
+    if (P.kind == k) { launch_force_kind<En>(c, P, pool, scratchE); return; } \
+    k++;
+    MISTARK_FOR_EACH_ENERGY(X)
+#undef X
+    throw Error("unknown potential kind");
+}
+
 // a contact / friction table that eval() may put into the shared launch (k_eval_pgh_multi): generic kernel, Hessian wanted; *np = lanes per row
 static bool joins_multi_pgh(const Context& c, const Potential& P, int* np)
 {

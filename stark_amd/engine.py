@@ -255,6 +255,44 @@ class Engine:
         self._ck(self.L.mistark_get_element_energies(self.h, pot, E.ctypes.data))
         return E
 
+    # ---- force readout (include/mistark.h "force readout") ------------------------------------------------------------------
+    def element_forces(self, pot: int, scale: float = 1.0):
+        """(forces [n_elem, NB, 3], block_rows [n_elem, NB]) of one potential at the current DoFs: -scale * dE_e/du per node of every
+        element (zeros for elements whose condition is off)."""
+        ne, nb = C.c_int64(), C.c_int32()
+        self._ck(self.L.mistark_potential_element_forces(self.h, pot, float(scale), None, None, C.byref(ne), C.byref(nb)))
+        f = np.zeros((ne.value, nb.value, 3))
+        rows = np.zeros((ne.value, nb.value), dtype=np.int32)
+        if ne.value:
+            self._ck(self.L.mistark_potential_element_forces(self.h, pot, float(scale), f.ctypes.data, rows.ctypes.data, C.byref(ne), C.byref(nb)))
+        return f, rows
+
+    @staticmethod
+    def _pot_list(pots):
+        ids = np.ascontiguousarray([] if pots is None else pots, dtype=np.int32).reshape(-1)
+        return ids, (ids.ctypes.data if ids.size else None)
+
+    def forces(self, pots=None, scale: float = 1.0) -> np.ndarray:
+        """f[ndofs] = -scale * sum over the listed potential ids of dE/du (None or empty: all potentials); bit-reproducible."""
+        ids, ptr = self._pot_list(pots)
+        f = np.zeros(self.ndofs)
+        self._ck(self.L.mistark_forces(self.h, ptr, ids.size, float(scale), f.ctypes.data))
+        return f
+
+    def forces_resultant(self, pots, scale, rows, positions=None, about=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """out[6]: the sum of the same forces over the block rows `rows` (list order) and, with `positions` (one per listed row), of their
+        moments (positions - about) x f; zeros for the moment otherwise."""
+        ids, ptr = self._pot_list(pots)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        if pos is not None and len(pos) != len(r):
+            raise ValueError("one position per listed row")
+        ab = np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        out = np.zeros(6)
+        self._ck(self.L.mistark_forces_resultant(self.h, ptr, ids.size, float(scale), r.ctypes.data if r.size else None, r.size,
+                                                 pos.ctypes.data if pos is not None and pos.size else None, ab.ctypes.data, out.ctypes.data))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)

@@ -131,6 +131,8 @@ def _lib():
         L.mistark_sim_set_contact_ccd.argtypes = [p, C.c_int, C.c_double]
         I64 = C.POINTER(C.c_int64)
         L.mistark_sim_get_ccd_info.argtypes = [p, I64, I64, I64, I64, I64, D]
+        L.mistark_sim_record_forces.argtypes = [p, C.c_char_p]
+        L.mistark_sim_get_forces.argtypes = [p, C.c_int, p, p]
         _bound = True
     return L
 
@@ -315,11 +317,15 @@ class Simulation:
     # ---- rigid bodies ---------------------------------------------------------------------------------------------------
     def add_rigid_box(self, label, mass, size) -> int:
         size = (size, size, size) if np.isscalar(size) else size
-        return self._ck(self.L.mistark_sim_add_rigid_box(self.h, label.encode(), mass, _d3(size)))
+        return self._count_rb(self._ck(self.L.mistark_sim_add_rigid_box(self.h, label.encode(), mass, _d3(size))))
+
+    def _count_rb(self, idx):
+        self._n_rb = max(getattr(self, "_n_rb", 0), idx + 1)  # (forces() sizes its rigid-body output by it)
+        return idx
 
     def rb_add(self, mass, inertia_local) -> int:
         """RigidBodies::add(mass, inertia) without a collision mesh."""
-        return self._ck(self.L.mistark_sim_rb_add(self.h, float(mass), _d3(np.asarray(inertia_local, dtype=float).reshape(9))))
+        return self._count_rb(self._ck(self.L.mistark_sim_rb_add(self.h, float(mass), _d3(np.asarray(inertia_local, dtype=float).reshape(9)))))
 
     def rb_add_force_at_centroid(self, rb, f):
         self._ck(self.L.mistark_sim_rb_add_force_at_centroid(self.h, rb, _d3(f)))
@@ -467,6 +473,24 @@ class Simulation:
         sel = {"x0": 1, "v0": 2}[which]
         arr = np.ascontiguousarray(arr, dtype=np.float64)
         self._ck(self.L.mistark_sim_set_points(self.h, sel, arr.ctypes.data))
+
+    # ---- force recording ---------------------------------------------------------------------------------------------------
+    def record_forces(self, groups):
+        """groups: a list of potential-name prefixes, one group per entry ("" = all potentials), or a comma-separated string; None switches
+        recording off. Every accepted step then keeps, per group, the nodal forces (Newtons) of the state it converged at."""
+        if groups is None:
+            self._ck(self.L.mistark_sim_record_forces(self.h, None))
+            return
+        text = groups if isinstance(groups, str) else ",".join(groups)
+        self._ck(self.L.mistark_sim_record_forces(self.h, text.encode()))
+
+    def forces(self, group=0):
+        """(points [n_points, 3], rigid bodies [n_rigid_bodies, 6] = force and torque) of group `group` at the last accepted step. The torque is the
+        generalised force conjugate to w1 * dt (the physical torque to first order in |w1| * dt)."""
+        pts = np.zeros((self.info().n_points, 3))
+        rb = np.zeros((getattr(self, "_n_rb", 0), 6))
+        self._ck(self.L.mistark_sim_get_forces(self.h, int(group), pts.ctypes.data if pts.size else None, rb.ctypes.data if rb.size else None))
+        return pts, rb
 
     def engine_handle(self):
         return C.c_void_p(self.L.mistark_sim_engine(self.h))
