@@ -87,7 +87,9 @@ int mistark_potential(mistark_ctx* ctx, const char* name, const int32_t* conn, i
  *             a Symbol op binds output 0 (the energy), Branch ops are the if (value > 0) / else / endif markers
  *   constants one double per op (used by ConstantFloat ops)
  *   cond_*    optional second sequence: the element is active iff its value is > 0 (Potential::get_condition, conditional potentials)
- * Bindings on DoF arrays define the local DoF blocks exactly as for mistark_potential. Limits: 96 inputs, 256 live temporaries. */
+ * Bindings on DoF arrays define the local DoF blocks exactly as for mistark_potential. Limits: 96 inputs, 256 live temporaries, Branch
+ * markers nested at most 32 deep. The markers of either sequence must nest (no else / endif without an open if, one else per if, none left
+ * open): anything else is refused here with the potential's name and the op index. */
 int mistark_potential_custom(mistark_ctx* ctx, const char* name, const int32_t* conn, int32_t n_elem, int32_t conn_stride, const mistark_binding* bindings, int32_t n_bindings,
                              const int32_t* ops, const double* constants, int32_t n_ops, int32_t n_inputs, const int32_t* cond_ops, const double* cond_constants,
                              int32_t n_cond_ops);

@@ -97,7 +97,11 @@ class D2:
 
     def powN(self, k: int):
         v = self.v
-        return self._chain(v ** k, k * v ** (k - 1), k * (k - 1) * v ** (k - 2) if k >= 2 else np.zeros_like(v))
+        if k == 0:
+            return D2.const(np.ones_like(v), self.n)
+        if k == 1:
+            return self
+        return self._chain(v ** k, k * v ** (k - 1), k * (k - 1) * v ** (k - 2))   # (k < 0 as well: the reciprocal powers)
 
     def sqrt(self):
         s = np.sqrt(self.v)
@@ -107,6 +111,27 @@ class D2:
     def log(self):
         r = 1.0 / self.v
         return self._chain(np.log(self.v), r, -r * r)
+
+    def log10(self):
+        return self.log() * (1.0 / np.log(10.0))
+
+    def exp(self):
+        e = np.exp(self.v)
+        return self._chain(e, e, e)
+
+    def powF(self, y):
+        """self ** y for self > 0, y a D2 or an array: exp(y ln self), differentiated through both."""
+        return (self.log() * y).exp()
+
+    def tan(self):
+        t = np.tan(self.v)
+        s = 1.0 + t * t
+        return self._chain(t, s, 2.0 * t * s)
+
+    def asin(self):
+        x = self.v
+        s = 1.0 / np.sqrt(1.0 - x * x)
+        return self._chain(np.arcsin(x), s, x * s * s * s)
 
     def acos(self):
         x = self.v

@@ -60,6 +60,8 @@ def run(ops, consts, inputs, n_elem):
             if t == SYMBOL:
                 r = get(a)
                 m = mask[-1]
+                if out is None and not m.all():
+                    out = np.zeros(n_elem)   # (the output is 0 until a Symbol op a lane executes sets it)
                 out = r if out is None or m.all() else (where(m, _lift(r, like), _lift(out, like)) if like is not None else np.where(m, r, out))
                 continue
             if t == ZERO: r = np.zeros(n_elem)
@@ -80,6 +82,26 @@ def run(ops, consts, inputs, n_elem):
             elif t == LN:
                 x = get(a)
                 r = x.log() if isinstance(x, D2) else np.where(x <= 0.0, -np.inf, np.log(np.where(x <= 0.0, 1.0, x)))
+            elif t == POWF:   # x^y = exp(y ln x): x > 0; either side may carry derivatives
+                x, y = get(a), get(b)
+                if isinstance(x, D2):
+                    r = x.powF(y)
+                elif isinstance(y, D2):
+                    r = (y * np.log(x)).exp()
+                else:
+                    r = np.exp(y * np.log(x))
+            elif t == LOG10:
+                x = get(a)
+                r = x.log10() if isinstance(x, D2) else np.where(x <= 0.0, -np.inf, np.log10(np.where(x <= 0.0, 1.0, x)))
+            elif t == EXP:
+                x = get(a)
+                r = x.exp() if isinstance(x, D2) else np.exp(x)
+            elif t == TAN:
+                x = get(a)
+                r = x.tan() if isinstance(x, D2) else np.tan(x)
+            elif t == ASIN:
+                x = get(a)
+                r = x.asin() if isinstance(x, D2) else np.arcsin(x)
             elif t == SIN:
                 x = get(a)
                 r = x.sin() if isinstance(x, D2) else np.sin(x)
@@ -94,7 +116,7 @@ def run(ops, consts, inputs, n_elem):
                 r = x.atan() if isinstance(x, D2) else np.arctan(x)
             elif t == PRINT: r = np.zeros(n_elem)
             else:
-                raise NotImplementedError("op type %d is not used by any fixture" % t)
+                raise NotImplementedError("op type %d is not an op of symx::ExprType" % t)   # (3 and whatever lies outside 0..22)
         put(dst, r)
     return out
 

@@ -28,6 +28,8 @@ enum : int32_t { OP_ZERO = 0, OP_ONE = 1, OP_BRANCH = 2, OP_CONST = 4, OP_SYMBOL
                  OP_LN = 13, OP_LOG10 = 14, OP_EXP = 15, OP_SIN = 16, OP_COS = 17, OP_TAN = 18, OP_ASIN = 19, OP_ACOS = 20, OP_ATAN = 21, OP_PRINT = 22 };
 constexpr int CUSTOM_MAX_REGS = 256;  // live temporaries after register allocation (EnergyTriangleStrain needs 70, the rigid-rigid contact potentials 206)
 constexpr int CUSTOM_MAX_IN = 96;     // gathered inputs per element
+constexpr int CUSTOM_MAX_DEPTH = 32;  // nested if / else / endif markers: one bit per open branch in the interpreter's 32-bit stacks
+static_assert(CUSTOM_MAX_DEPTH <= 32, "run_program keeps the branch stacks in uint32_t: bit `depth` is written for depth < CUSTOM_MAX_DEPTH");
 
 struct CustomProgram
 {
@@ -79,7 +81,8 @@ __device__ HDual run_program(const int32_t* __restrict__ ops, const double* __re
         return reg[idx - n_in];
     };
     HDual out(0.0);
-    // if / else / endif markers: a stack of (parent active, branch taken) bits; ops of an inactive region are skipped per lane
+    // if / else / endif markers: a stack of (parent active, branch taken) bits; ops of an inactive region are skipped per lane.
+    // validate_branches has refused unbalanced markers and nesting beyond CUSTOM_MAX_DEPTH: 0 <= depth < 32 at every shift below
     uint32_t parent = 0, taken = 0;
     int depth = 0;
     bool active = true;
@@ -205,10 +208,36 @@ __global__ __launch_bounds__(256) void k_eval_custom(PotArgs a, ProgDev p, doubl
     if (first) elemE[pe] = energy_here(a, e) ? r.v : 0.0;  // (sharded runs: an interface element is evaluated by every rank that owns one of its rows; its energy counts once)
 }
 
+// The if / else / endif markers of one op sequence must nest: the interpreter indexes its bit stacks with the depth and the emitter turns
+// them into braces, so an `else` or `endif` without an open `if`, a second `else`, an `if` left open or nesting beyond CUSTOM_MAX_DEPTH
+// is refused at registration.
+void validate_branches(const std::vector<int32_t>& ops, int n_ops, const std::string& name)
+{
+    std::vector<char> has_else;  // per open if
+    auto at = [&](int k) { return "custom potential '" + name + "': op " + std::to_string(k); };
+    for (int k = 0; k < n_ops; k++) {
+        const int32_t* op = &ops[5 * (size_t)k];
+        if (op[0] != OP_BRANCH) continue;
+        if (op[4] == -2) {  // endif
+            if (has_else.empty()) throw Error(at(k) + " is an endif without an open if");
+            has_else.pop_back();
+        } else if (op[2] == 0) {  // if
+            if ((int)has_else.size() == CUSTOM_MAX_DEPTH) throw Error(at(k) + " nests branches deeper than " + std::to_string(CUSTOM_MAX_DEPTH));
+            has_else.push_back(0);
+        } else {  // else
+            if (has_else.empty()) throw Error(at(k) + " is an else without an open if");
+            if (has_else.back()) throw Error(at(k) + " is a second else for one if");
+            has_else.back() = 1;
+        }
+    }
+    if (!has_else.empty()) throw Error(at(n_ops - 1) + " ends the sequence with " + std::to_string(has_else.size()) + " if still open");
+}
+
 // Linear-scan register allocation of the temporaries of one op sequence (values >= n_in). A value defined in both arms of a branch
 // gets one register: its live range runs from its first definition to its last use.
 void allocate_registers(std::vector<int32_t>& ops, int n_ops, int n_in, int& n_regs, const std::string& name)
 {
+    validate_branches(ops, n_ops, name);
     int max_val = n_in;
     auto reads = [&](const int32_t* op, int* out) {  // value indices an op reads
         int k = 0;

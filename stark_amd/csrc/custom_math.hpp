@@ -10,9 +10,9 @@ namespace mistark {
 __device__ __forceinline__ HDual cop_pown(const HDual& x, int n)
 {
     if (n == 0) return HDual(1.0);
-    const double p2 = ::pow(x.v, (double)(n - 2)), p1 = p2 * x.v;  // x^(n-2), x^(n-1)
     if (n == 1) return x;
     if (n == 2) return x * x;
+    const double p2 = ::pow(x.v, (double)(n - 2)), p1 = p2 * x.v;  // x^(n-2), x^(n-1)
     return chain(x, p1 * x.v, n * p1, (double)n * (n - 1) * p2);
 }
 __device__ __forceinline__ HDual cop_powf(const HDual& x, const HDual& y)
