@@ -165,6 +165,25 @@ int mistark_forces(mistark_ctx* ctx, const int32_t* potentials, int32_t n, doubl
 int mistark_forces_resultant(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double scale, const int32_t* rows, int64_t n_rows,
                              const double* pos_host, const double about[3], double out[6]);
 
+/* ---- stress readout -------------------------------------------------------------------------------------------------------
+ * Stress and strain of the elements of the six strain potentials (EnergyTetStrain, EnergyTriangleStrain, EnergySegmentStrain and their
+ * _Elasticity_Only variants) at the end-of-step state x1 = x0 + dt v1 of the current DoFs. A pipeline of its own beside mistark_eval, like the force
+ * readout: it writes only buffers of its own, uses no floating-point atomics (two readouts of one state give the same bits) and costs nothing unless it
+ * is called. One record is 16 doubles, the same for the three kinds:
+ *   0..5 Cauchy stress in the world frame (xx yy zz xy yz zx, Pa) | 6 von Mises stress | 7 mean stress tr(sigma)/3 | 8 J (volume, area or length ratio)
+ *   9..11 principal stretches, descending (a triangle has two, a segment one; the rest are 0) | 12 largest principal Green strain (stretch_max^2 - 1)/2
+ *   13 energy density psi (J/m^3) as the potential evaluates it: elastic + damping + strain limiting, without the triangle's inflation term
+ *   14 rest measure m, element energy = m * psi: det(DX)/6, thickness * rest area, pi r^2 l_rest | 15 flags: +1 strain limiting active, +2 degenerate
+ * A triangle's stress is F S F^T / J, a symmetric world-frame tensor tangent to the deformed triangle; a segment's is (N / (pi r^2)) t t^T. Degenerate
+ * elements (J <= 0, det C <= 0, zero length) set flag 2 and report zeros in 0..7 and 12. Refused, with the cause in the message: sharded contexts
+ * (single-rank accessor), registration-only contexts, any other potential (by name), and a nodal list that mixes kinds. */
+/* out[e][16], e < n_elem (nullable: query n_elem and kind = 0 tet, 1 triangle, 2 segment). */
+int mistark_potential_element_stress(mistark_ctx* ctx, int potential, double* out, int64_t* n_elem, int32_t* kind);
+/* out_host[block row][10]: the averages of fields 0..8 over the listed potentials' elements at the row, weighted with the rest measure m, then the weight
+ * sum; summed in a fixed order (bit-reproducible). Entry 6 is the AVERAGE OF THE ELEMENTS' von Mises values, not the von Mises value of the averaged
+ * tensor. Rows nobody touches are ten zeros. The listed potentials must be of one kind (the weights of different kinds have different units). */
+int mistark_nodal_stress(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out_host);
+
 /* ---- projection + assembly ------------------------------------------------------------------------------------------ */
 /* ElementHessians::project_to_PD_inplace__all / project_to_PD_for_update__selectively (ElementHessians.cpp:48-67,79-182;
  * project_to_PD.cpp:12-32). active_blocks: NULL = all elements, else ndofs/3 flags; only not-yet-projected elements
@@ -375,7 +394,8 @@ int mistark_sync(mistark_ctx* ctx);
  * the one-lane / one-wavefront / 64-wavefront gather kernel, by the length of their contribution lists), "llt_path" / "llt_panel_rows" /
  * "llt_panels" / "llt_fronts" (the last DirectLLT solve: 0 dense, 1 band, 2 multifrontal, -1 none yet; block rows per panel — multifrontal: of the
  * largest front —, panels, fronts), "force_readouts" (force readout calls that launched) / "force_long_rows" (block rows of the last readout
- * that were summed by a whole wavefront: more than 256 contributions). */
+ * that were summed by a whole wavefront: more than 256 contributions), "stress_readouts" / "stress_long_rows" (the same two for the stress readout:
+ * calls that launched, rows of the last nodal readout summed by a whole wavefront). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

@@ -220,6 +220,14 @@ int mistark_sim_record_forces(mistark_sim* sim, const char* groups);
  * of the DoF sets v1 and w1 (nullable outputs). The torque is the generalised force conjugate to w1 * dt; it equals the physical torque to first
  * order in |w1| * dt (the rotation of a step is integrated from w1 through a quaternion update, not linearly). */
 int mistark_sim_get_forces(mistark_sim* sim, int group, double* points_out, double* rb_out);
+/* Stress recording (off by default; not in the reference), at the same place inside the step: per kind (0 tet, 1 triangle, 2 segment) one element readout
+ * over that kind's potentials — potential id ascending, then element — and one nodal readout (mistark.h "stress readout": records of 16 doubles, nodal
+ * rows of 10). Results stay on the device until they are asked for. With recording off nothing is registered, launched or allocated. */
+int mistark_sim_record_stress(mistark_sim* sim, int enabled);
+/* elem_out [n_elem x 16] of the last accepted step (nullable: query n_elem) */
+int mistark_sim_get_stress(mistark_sim* sim, int kind, double* elem_out, int64_t* n_elem);
+/* points_out [n_points x 10]: the nodal averages at the points' rows (points no element of the kind touches: ten zeros) */
+int mistark_sim_get_nodal_stress(mistark_sim* sim, int kind, double* points_out);
 /* The part of a time step before the Newton solve (Stark.cpp:145-156: before_time_step callbacks = friction tables at the start-of-step
  * geometry, rigid-body caches, v1 = 0) and the Newton callback that precedes every evaluation (contact tables at the current DoFs), as
  * separate calls: what the reference's harness does to take a stage snapshot at a given state (callbacks->run_before_time_step();

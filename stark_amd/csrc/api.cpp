@@ -577,6 +577,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "asm_vlong_slots_0" || n == "asm_vlong_slots_1") { ensure_pattern(c); *out = c.part[n.back() - '0'].n_vlong; }
     else if (n == "force_readouts") *out = c.n_force_readouts;
     else if (n == "force_long_rows") *out = force_long_rows(c);
+    else if (n == "stress_readouts") *out = c.n_stress_readouts;
+    else if (n == "stress_long_rows") *out = stress_long_rows(c);
     else if (n == "llt_path") *out = c.llt_last_path;
     else if (n == "llt_panel_rows") *out = c.llt_last_panel_rows;
     else if (n == "llt_panels") *out = c.llt_last_panels;
@@ -714,6 +716,20 @@ int mistark_forces_resultant(mistark_ctx* ctx, const int32_t* potentials, int32_
 {
     API_BEGIN
     force_resultant_host(ctx->c, potentials, n, scale, rows, n_rows, pos_host, about, out);
+    API_END(0)
+}
+
+// ---- stress readout (stress.hip) ---------------------------------------------------------------------------------------
+int mistark_potential_element_stress(mistark_ctx* ctx, int potential, double* out, int64_t* n_elem, int32_t* kind)
+{
+    API_BEGIN
+    stress_elements_host(ctx->c, potential, out, n_elem, kind);
+    API_END(0)
+}
+int mistark_nodal_stress(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out_host)
+{
+    API_BEGIN
+    stress_nodal_host(ctx->c, potentials, n, out_host);
     API_END(0)
 }
 
@@ -1382,6 +1398,24 @@ int force_fetch(mistark_ctx* ctx, int slot, double* f_host, int64_t ndofs)
 {
     API_BEGIN
     force_fetch_slot(ctx->c, slot, f_host, ndofs);
+    API_END(0)
+}
+int stress_record(mistark_ctx* ctx, int kind)
+{
+    API_BEGIN
+    stress_record_kind(ctx->c, kind);
+    API_END(0)
+}
+int stress_fetch(mistark_ctx* ctx, int kind, double* out, int64_t* n_elem)
+{
+    API_BEGIN
+    stress_fetch_elements(ctx->c, kind, out, n_elem);
+    API_END(0)
+}
+int stress_fetch_nodal(mistark_ctx* ctx, int kind, double* out, int64_t n_rows)
+{
+    API_BEGIN
+    mistark::stress_fetch_nodal(ctx->c, kind, out, n_rows);
     API_END(0)
 }
 }  // namespace mistark

@@ -539,6 +539,23 @@ struct Context
     int64_t n_force_readouts = 0;   // counter "force_readouts": readout calls that launched
     bool fr_stat_valid = false;
 
+    // Stress readout (stress.hip): a pipeline beside eval() like the force readout, with buffers of its own. Element records field-major in sr_rec
+    // ([16][elements of the selection]), contributions (element, local block) sorted by block row, one ordered weighted sum per row -> sr_out [nbr][10].
+    DevBuf<double> sr_rec, sr_out;
+    DevBuf<uint32_t> sr_key, sr_key_alt, sr_val, sr_val_alt;
+    DevBuf<uint32_t> sr_stat;        // [0]: rows of the last nodal readout summed by a whole wavefront (counter "stress_long_rows")
+    DevBuf<unsigned char> sr_desc;
+    DevBuf<uint8_t> sr_cub_tmp;
+    struct StressSlot                // what the host mirror records per kind inside a time step and keeps on the device
+    {
+        DevBuf<double> rec, nodal;
+        int64_t n_elem = -1;         // elements recorded (-1: nothing yet)
+        int64_t nbr = 0;
+    };
+    StressSlot stress_slots[3];
+    int64_t n_stress_readouts = 0;  // counter "stress_readouts": readout calls that launched
+    bool sr_stat_valid = false;
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -636,6 +653,13 @@ void force_resultant_host(Context& c, const int32_t* pots, int32_t n, double sca
 int64_t force_long_rows(Context& c);  // counter "force_long_rows"
 void force_record_slot(Context& c, int slot, const int32_t* pots, int32_t n, bool all, double scale);
 void force_fetch_slot(Context& c, int slot, double* f_host, int64_t n);
+// Stress readout (stress.hip, records as stress.hpp lays them out). kind: 0 tet, 1 triangle, 2 segment.
+void stress_elements_host(Context& c, int pot, double* out, int64_t* n_elem, int32_t* kind);
+void stress_nodal_host(Context& c, const int32_t* pots, int32_t n, double* out_host);
+int64_t stress_long_rows(Context& c);  // counter "stress_long_rows"
+void stress_record_kind(Context& c, int kind);  // every potential of the kind, id ascending: element records and nodal averages into Context::stress_slots[kind]
+void stress_fetch_elements(Context& c, int kind, double* out, int64_t* n_elem);
+void stress_fetch_nodal(Context& c, int kind, double* out, int64_t n_rows);
 int find_kind(const char* name);
 int kind_nb(int kind);
 int kind_nbind(int kind);

@@ -8,29 +8,9 @@
 //   3. resultants     : sum of force and moment over a caller's list of block rows, in list order (k_force_resultant)
 // No floating-point atomics anywhere: two readouts of one state give the same bits.
 #include "kernels_common.hpp"
+#include "force_keys.hpp"
 
 namespace mistark {
-
-struct ForceDesc
-{
-    const int32_t* conn;
-    int stride, n_elem, NB;
-    uint32_t g_off;  // first contribution of the potential: g = g_off + block * n_elem + element, the pool holds 3 doubles per contribution
-    int dof_col[MAX_NB], dof_row_off[MAX_NB];
-};
-// contribution g -> (block row, g)
-__global__ __launch_bounds__(BLOCK) void k_force_keys(const ForceDesc* __restrict__ D, int n_desc, int64_t total, uint32_t* __restrict__ key, uint32_t* __restrict__ val)
-{
-    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= total) return;
-    int k = 0;
-    while (k + 1 < n_desc && g >= (int64_t)D[k + 1].g_off) k++;
-    const ForceDesc& d = D[k];
-    const uint32_t l = (uint32_t)g - d.g_off;
-    const int b = (int)(l / (uint32_t)d.n_elem), e = (int)(l - (uint32_t)b * (uint32_t)d.n_elem);
-    key[g] = (uint32_t)(d.dof_row_off[b] + d.conn[(size_t)e * d.stride + d.dof_col[b]]);
-    val[g] = (uint32_t)g;
-}
 
 // Segmented sum over the sorted contributions: one lane per sorted position; the lane at the head of a row's run sums the run in order and writes
 // f[row] = -scale * sum. Runs beyond FORCE_LONG_ROW (a rigid body attached to hundreds of points, or under thousands of contacts) are summed by the

@@ -422,9 +422,14 @@ Line::Handler DeformablesPresets::add_line(const std::string& label, const std::
 {
     PointSetHandler ps = deformables->point_sets->add(V, label);
     auto inertia = deformables->lumped_inertia->add(ps, segments, p.inertia);
-    auto strain = deformables->segment_strain->add(ps, segments, p.strain);
+    auto seg = deformables->segment_strain;
+    const size_t pos = p.strain.elasticity_only ? seg->n_elasticity_only() : seg->n_complete();  // (cells and elements are both `segments`, in order)
+    auto strain = seg->add(ps, segments, p.strain);
     ContactHandler contact = interactions->contact->add_edges(ps, segments, p.contact);
-    if (!label.empty() && interactions->output) interactions->output->add_segment_mesh(label, ps, segments);
+    if (!label.empty() && interactions->output) {
+        interactions->output->add_segment_mesh(label, ps, segments);
+        interactions->output->set_stress_source(2, p.strain.elasticity_only, pos, [seg]() { return seg->n_complete(); });
+    }
     return {ps, inertia, strain, contact};
 }
 Line::VCH DeformablesPresets::add_line_as_segments(const std::string& label, const Vec3& begin, const Vec3& end, int n_segments, const Line::Params& p)

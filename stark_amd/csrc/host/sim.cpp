@@ -54,6 +54,7 @@ void Stark::ensure_registered()
     force_set_points = force_set_rb_v = force_set_rb_w = -1;
     force_n_points = force_n_rb = 0;
     forces_recorded = false;  // (recorded vectors live in the context just replaced)
+    stress_recorded = false;
     for (auto* m : models) m->register_dofs(ctx);
     dt_array_id = mistark_array(ctx, &dt, 1, 1);
     check(dt_array_id);
@@ -190,6 +191,10 @@ bool Stark::run_one_step()
             }
             forces_recorded = true;
         }
+        if (stress_recording) {
+            for (int kind = 0; kind < 3; kind++) check(stress_record(ctx, kind));
+            stress_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -253,6 +258,29 @@ void Stark::get_forces(int group, double* points_out, double* rb_out)
                 rb_out[6 * b + 3 + d] = f[(size_t)(3 * (rw + b) + d)];
             }
     }
+}
+void Stark::record_stress(bool enabled)
+{
+    stress_recording = enabled;
+    stress_recorded = false;
+}
+void Stark::get_stress(int kind, double* elem_out, int64_t* n_elem)
+{
+    if (!stress_recording) throw std::runtime_error("get_stress: stress recording is off (record_stress)");
+    if (!ctx || !stress_recorded) throw std::runtime_error("get_stress: no time step has been accepted since recording was switched on");
+    check(stress_fetch(ctx, kind, elem_out, n_elem));
+}
+void Stark::get_nodal_stress(int kind, double* points_out)
+{
+    if (!stress_recording) throw std::runtime_error("get_nodal_stress: stress recording is off (record_stress)");
+    if (!ctx || !stress_recorded) throw std::runtime_error("get_nodal_stress: no time step has been accepted since recording was switched on");
+    if (!points_out || force_n_points <= 0) return;
+    const int64_t nbr = mistark_ndofs(ctx) / 3;
+    std::vector<double> all((size_t)nbr * 10);
+    check(stress_fetch_nodal(ctx, kind, all.data(), nbr));
+    const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
+    if (r0 < 0) throw std::runtime_error("get_nodal_stress: the point set has no DoFs");
+    std::copy(all.begin() + 10 * r0, all.begin() + 10 * (r0 + force_n_points), points_out);
 }
 std::string Stark::get_frame_path(const std::string& name) const
 {
@@ -918,10 +946,15 @@ Surface::Handler DeformablesPresets::add_surface(const std::string& label, const
     // DeformablesPresets.cpp:31-44
     PointSetHandler ps = deformables->point_sets->add(V, label);
     auto inertia = deformables->lumped_inertia->add(ps, T, p.inertia);
-    auto strain = deformables->triangle_strain->add(ps, T, p.strain);
+    auto tri = deformables->triangle_strain;
+    const size_t pos = p.strain.elasticity_only ? tri->n_elasticity_only() : tri->n_complete();  // (cells and elements are both T, in order)
+    auto strain = tri->add(ps, T, p.strain);
     auto bending = deformables->discrete_shells->add(ps, T, p.bending);
     ContactHandler contact = interactions->contact->add_triangles(ps, T, p.contact);
-    if (!label.empty() && interactions->output) interactions->output->add_triangle_mesh(label, ps, T);
+    if (!label.empty() && interactions->output) {
+        interactions->output->add_triangle_mesh(label, ps, T);
+        interactions->output->set_stress_source(1, p.strain.elasticity_only, pos, [tri]() { return tri->n_complete(); });
+    }
     return {ps, inertia, strain, bending, contact};
 }
 Surface::VCH DeformablesPresets::add_surface_grid(const std::string& label, const std::array<double, 2>& dim, const std::array<int, 2>& sub, const Surface::Params& p)
@@ -937,7 +970,9 @@ Volume::Handler DeformablesPresets::add_volume(const std::string& label, const s
     // DeformablesPresets.cpp:65-79: the collision mesh is the surface of the tet mesh
     PointSetHandler ps = deformables->point_sets->add(V, label);
     auto inertia = deformables->lumped_inertia->add(ps, T, p.inertia);
-    auto strain = deformables->tet_strain->add(ps, T, p.strain);
+    auto tet = deformables->tet_strain;
+    const size_t pos = p.strain.elasticity_only ? tet->n_elasticity_only() : tet->n_complete();  // (the potential's elements are T, in order)
+    auto strain = tet->add(ps, T, p.strain);
     ContactHandler contact;
     std::vector<std::array<int, 3>> surface;
     std::vector<int> tri_to_tet_map;
@@ -945,7 +980,29 @@ Volume::Handler DeformablesPresets::add_volume(const std::string& label, const s
     if (interactions->contact->is_active() || with_output) find_surface(surface, tri_to_tet_map, V, T);
     if (interactions->contact->is_active()) contact = interactions->contact->add_triangles(ps, surface, tri_to_tet_map, p.contact);
     // the frame of a volume is its surface with the surface's own vertices (DeformablesPresets.cpp:74-76)
-    if (with_output) interactions->output->add_triangle_mesh(label, ps, surface, tri_to_tet_map);
+    if (with_output) {
+        interactions->output->add_triangle_mesh(label, ps, surface, tri_to_tet_map);
+        // a surface triangle shows the one tet it is a face of
+        std::vector<std::array<int, 4>> faces;  // sorted vertex triple, tet
+        for (size_t t = 0; t < T.size(); t++)
+            for (int skip = 0; skip < 4; skip++) {
+                std::array<int, 4> f{};
+                int k = 0;
+                for (int a = 0; a < 4; a++)
+                    if (a != skip) f[k++] = T[t][a];
+                std::sort(f.begin(), f.begin() + 3);
+                f[3] = (int)t;
+                faces.push_back(f);
+            }
+        std::sort(faces.begin(), faces.end());
+        std::vector<int> cell_tet(surface.size());
+        for (size_t c = 0; c < surface.size(); c++) {
+            std::array<int, 4> f = {tri_to_tet_map[surface[c][0]], tri_to_tet_map[surface[c][1]], tri_to_tet_map[surface[c][2]], -1};
+            std::sort(f.begin(), f.begin() + 3);
+            cell_tet[c] = (*std::lower_bound(faces.begin(), faces.end(), f))[3];
+        }
+        interactions->output->set_stress_source(0, p.strain.elasticity_only, pos, [tet]() { return tet->n_complete(); }, std::move(cell_tet));
+    }
     return {ps, inertia, strain, contact};
 }
 Volume::VCH DeformablesPresets::add_volume_grid(const std::string& label, const Vec3& dim, const std::array<int, 3>& sub, const Volume::Params& p)

@@ -143,6 +143,13 @@ public:
     // vectors stay on the device until get_forces() downloads one. Off: nothing is registered, launched or allocated.
     void record_forces(const char* groups);  // comma-separated name prefixes, one group per entry ("" = all potentials); nullptr: off
     void get_forces(int group, double* points_out /* n_points x 3, nullable */, double* rb_out /* n_rb x 6: force, torque; nullable */);
+    // Stress recording (off by default; not in the reference): at the same place, per kind (0 tet, 1 triangle, 2 segment) one element readout over that
+    // kind's potentials (potential id ascending, then element) and one nodal readout (include/mistark.h "stress readout"); kept on the device until asked
+    // for. Off: nothing is registered, launched or allocated.
+    void record_stress(bool enabled);
+    void get_stress(int kind, double* elem_out /* n_elem x 16, nullable */, int64_t* n_elem);
+    void get_nodal_stress(int kind, double* points_out /* n_points x 10 */);
+    bool stress_recording = false, stress_recorded = false;
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -317,6 +324,10 @@ public:
     void set_params(const Handler& h, const Params& p);
     void register_potentials(mistark_ctx* ctx) override;
 
+    // elements registered so far per potential (the stress readout of the frames: a mesh's elements are a run in one of the two tables)
+    size_t n_complete() const { return conn_complete.size(); }
+    size_t n_elasticity_only() const { return conn_elasticity_only.size(); }
+
 private:
     Stark& stark;
     spPointDynamics dyn;
@@ -341,6 +352,10 @@ public:
     void set_params(const Handler& h, const Params& p);
     void register_potentials(mistark_ctx* ctx) override;
 
+    // elements registered so far per potential (the stress readout of the frames: a mesh's elements are a run in one of the two tables)
+    size_t n_complete() const { return conn_complete.size(); }
+    size_t n_elasticity_only() const { return conn_elasticity_only.size(); }
+
 private:
     Stark& stark;
     spPointDynamics dyn;
@@ -364,6 +379,10 @@ public:
     Params get_params(const Handler& h) const;
     void set_params(const Handler& h, const Params& p);
     void register_potentials(mistark_ctx* ctx) override;
+
+    // elements registered so far per potential (the stress readout of the frames: a mesh's elements are a run in one of the two tables)
+    size_t n_complete() const { return conn_complete.size(); }
+    size_t n_elasticity_only() const { return conn_elasticity_only.size(); }
 
 private:
     Stark& stark;
@@ -721,7 +740,13 @@ struct Interactions
 // ---- frame output (stark/src/models/deformables/DeformablesMeshOutput.*, rigidbodies/RigidBodiesMeshOutput.*) ------
 // Legacy binary VTK files, one per output label and frame, written from the host mirror of the state (positions leave the device once
 // per frame, not per step). Meshes with the same label are merged into one file.
-void write_VTK(const std::string& path, const std::vector<Vec3>& vertices, const int* conn, size_t n_cells, int nodes_per_cell);
+// cell data of a frame written while stress recording is on: per cell von Mises stress, mean stress, largest principal stretch and the Cauchy tensor
+// (row-major 3 x 3), as floats; cells that show no strain element (rigid bodies, point clouds) hold zeros
+struct FrameCellData
+{
+    std::vector<float> von_mises, mean_stress, stretch_max, cauchy;
+};
+void write_VTK(const std::string& path, const std::vector<Vec3>& vertices, const int* conn, size_t n_cells, int nodes_per_cell, const FrameCellData* cells = nullptr);
 class MeshOutput
 {
 public:
@@ -734,11 +759,21 @@ public:
     void add_triangle_mesh(const std::string& label, const PointSetHandler& set, const std::vector<std::array<int, 3>>& conn, const std::vector<int>& point_set_map);
     void add_tet_mesh(const std::string& label, const PointSetHandler& set, const std::vector<std::array<int, 4>>& conn);
     void add_triangle_mesh(const std::string& label, const RigidBodyHandler& rb, const std::vector<Vec3>& local_vertices, const std::vector<std::array<int, 3>>& conn);
+    // Stress recording (Stark::record_stress): the mesh added last shows the elements of one strain potential. kind 0 tet / 1 triangle / 2 segment;
+    // its elements are the run from `pos` on in the kind's complete or elasticity-only table, whose order is the potential's element order; n_complete()
+    // of the model at write time places the elasticity-only table behind the complete one (the order of Stark::get_stress). cell_elem: element of the run
+    // per cell (the surface triangles of a volume -> their tets); empty: cell c shows element c.
+    void set_stress_source(int kind, bool elasticity_only, size_t pos, std::function<size_t()> n_complete, std::vector<int> cell_elem = {});
     int frames_written = 0;
 
 private:
     struct Mesh
     {
+        int stress_kind = -1;
+        bool stress_eo = false;
+        size_t stress_pos = 0;
+        std::function<size_t()> stress_n_complete;
+        std::vector<int> cell_elem;
         std::string label;
         int nodes_per_cell = 0;
         int point_set = -1, rigid_body = -1;

@@ -749,6 +749,24 @@ int mistark_sim_get_forces(mistark_sim* s, int group, double* points_out, double
     s->sim->get_stark().get_forces(group, points_out, rb_out);
     SIM_END
 }
+int mistark_sim_record_stress(mistark_sim* s, int enabled)
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_stress(enabled != 0);
+    SIM_END
+}
+int mistark_sim_get_stress(mistark_sim* s, int kind, double* elem_out, int64_t* n_elem)
+{
+    SIM_BEGIN
+    s->sim->get_stark().get_stress(kind, elem_out, n_elem);
+    SIM_END
+}
+int mistark_sim_get_nodal_stress(mistark_sim* s, int kind, double* points_out)
+{
+    SIM_BEGIN
+    s->sim->get_stark().get_nodal_stress(kind, points_out);
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

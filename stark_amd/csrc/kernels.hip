@@ -67,19 +67,6 @@ void kind_strides(int kind, int* out) { std::memcpy(out, kinds()[kind].strides, 
 // ======================================================================================================================
 // Element evaluation
 // ======================================================================================================================
-template <class En>
-__device__ __forceinline__ void gather_inputs(const PotArgs& a, int e, double* in)
-{
-    const int32_t* ce = a.conn + (size_t)e * a.conn_stride;
-    En::Layout::for_each([&](int b, int S, int o) {
-        const int col = a.conn_col[b];
-        const size_t idx = col < 0 ? 0 : (size_t)ce[col];
-        const double* src = a.arr[b] + idx * S;
-#pragma unroll
-        for (int c = 0; c < S; c++) in[o + c] = src[c];
-    });
-}
-
 // Energy only: one lane per element
 template <class En>
 __global__ __launch_bounds__(BLOCK) void k_eval_p(PotArgs a, double* __restrict__ elemE)

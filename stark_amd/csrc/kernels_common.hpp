@@ -100,6 +100,20 @@ __device__ __forceinline__ void sum_partials2(const double* __restrict__ pa, con
     b = sm[4] + sm[5] + sm[6] + sm[7];
 }
 
+// the bound inputs of element e in binding order (En::Layout of energies.hpp): what every element kernel starts from
+template <class En>
+__device__ __forceinline__ void gather_inputs(const PotArgs& a, int e, double* in)
+{
+    const int32_t* ce = a.conn + (size_t)e * a.conn_stride;
+    En::Layout::for_each([&](int b, int S, int o) {
+        const int col = a.conn_col[b];
+        const size_t idx = col < 0 ? 0 : (size_t)ce[col];
+        const double* src = a.arr[b] + idx * S;
+#pragma unroll
+        for (int c = 0; c < S; c++) in[o + c] = src[c];
+    });
+}
+
 constexpr uint32_t NO_SRC = 0xFFFFFFFFu;
 constexpr int CHUNK_BLOCKS = 256;
 constexpr int DYN_SHORT_ROW = 32;  // contact rows of a node hold a handful of blocks; only the rows of rigid bodies in contact are long

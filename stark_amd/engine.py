@@ -293,6 +293,23 @@ class Engine:
                                                  pos.ctypes.data if pos is not None and pos.size else None, ab.ctypes.data, out.ctypes.data))
         return out
 
+    # ---- stress readout (include/mistark.h "stress readout") ----------------------------------------------------------------
+    def element_stress(self, pot: int):
+        """(records [n_elem, 16], kind) of one strain potential at the current DoFs; kind 0 tet, 1 triangle, 2 segment. Record layout: mistark.h."""
+        ne, kind = C.c_int64(), C.c_int32()
+        self._ck(self.L.mistark_potential_element_stress(self.h, pot, None, C.byref(ne), C.byref(kind)))
+        rec = np.zeros((ne.value, 16))
+        if ne.value:
+            self._ck(self.L.mistark_potential_element_stress(self.h, pot, rec.ctypes.data, C.byref(ne), C.byref(kind)))
+        return rec, kind.value
+
+    def nodal_stress(self, pots) -> np.ndarray:
+        """out[block rows, 10]: rest-measure-weighted averages of record fields 0..8 over the listed potentials (one kind), then the weight sum."""
+        ids, ptr = self._pot_list(pots)
+        out = np.zeros((self.ndofs // 3, 10))
+        self._ck(self.L.mistark_nodal_stress(self.h, ptr, ids.size, out.ctypes.data))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)

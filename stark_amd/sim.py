@@ -133,6 +133,9 @@ def _lib():
         L.mistark_sim_get_ccd_info.argtypes = [p, I64, I64, I64, I64, I64, D]
         L.mistark_sim_record_forces.argtypes = [p, C.c_char_p]
         L.mistark_sim_get_forces.argtypes = [p, C.c_int, p, p]
+        L.mistark_sim_record_stress.argtypes = [p, C.c_int]
+        L.mistark_sim_get_stress.argtypes = [p, C.c_int, p, C.POINTER(C.c_int64)]
+        L.mistark_sim_get_nodal_stress.argtypes = [p, C.c_int, p]
         _bound = True
     return L
 
@@ -491,6 +494,24 @@ class Simulation:
         rb = np.zeros((getattr(self, "_n_rb", 0), 6))
         self._ck(self.L.mistark_sim_get_forces(self.h, int(group), pts.ctypes.data if pts.size else None, rb.ctypes.data if rb.size else None))
         return pts, rb
+
+    # ---- stress recording --------------------------------------------------------------------------------------------------
+    def record_stress(self, on=True):
+        """Every accepted step then keeps, per element kind, the stress records and nodal averages of the state it converged at (on the device)."""
+        self._ck(self.L.mistark_sim_record_stress(self.h, int(bool(on))))
+
+    def stress(self, kind=0):
+        """(records [n_elem, 16], nodal [n_points, 10]) of kind 0 tet / 1 triangle / 2 segment at the last accepted step: the elements of that kind's
+        potentials in potential order, then element order; layout in include/mistark.h "stress readout"."""
+        n = C.c_int64()
+        self._ck(self.L.mistark_sim_get_stress(self.h, int(kind), None, C.byref(n)))
+        rec = np.zeros((n.value, 16))
+        if n.value:
+            self._ck(self.L.mistark_sim_get_stress(self.h, int(kind), rec.ctypes.data, C.byref(n)))
+        nodal = np.zeros((self.info().n_points, 10))
+        if nodal.size:
+            self._ck(self.L.mistark_sim_get_nodal_stress(self.h, int(kind), nodal.ctypes.data))
+        return rec, nodal
 
     def engine_handle(self):
         return C.c_void_p(self.L.mistark_sim_engine(self.h))
