@@ -184,6 +184,27 @@ int mistark_potential_element_stress(mistark_ctx* ctx, int potential, double* ou
  * tensor. Rows nobody touches are ten zeros. The listed potentials must be of one kind (the weights of different kinds have different units). */
 int mistark_nodal_stress(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out_host);
 
+/* ---- budget readout -------------------------------------------------------------------------------------------------------
+ * Energies per potential and the mass, momentum and energy record of every object at the current DoFs. A pipeline of its own beside mistark_eval, like
+ * the force and stress readouts: it writes only buffers of its own, uses no floating-point atomics and costs nothing unless it is called. Every sum runs
+ * over fixed chunks of the element list in list order and through a fixed tree: a result depends on the order of the list alone, never on a grid size,
+ * the device or the run (two readouts of one state give the same bits). Contact and friction tables are read as installed (no search runs). Refused,
+ * with the cause in the message: sharded contexts (single-rank accessor), registration-only contexts, user-defined potentials, bad and duplicate ids.
+ * One record is 13 doubles, at the end-of-step state x = x0 + dt v1, v = v1:
+ *   0 mass sum m | 1..3 first moment sum m x | 4..6 linear momentum sum m v | 7..9 angular momentum sum (x - about) x (m v) (+ J1 w1 for a rigid body)
+ *   10 kinetic energy 0.5 sum m v.v (+ 0.5 w1.J1 w1) | 11 gravitational energy -sum m gravity.x | 12 item count */
+/* out[k] = the energy of potential potentials[k] (n = 0: of every potential, out[number of potentials]): the sum of the element energies mistark_eval
+ * would compute, elements whose condition is off counting zero, empty tables 0. */
+int mistark_energies(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out);
+/* out[g][13], g < n_groups: the record of every group of an EnergyLumpedInertia potential (any other is refused by name). An element's mass is
+ * lumped volume * density as the potential has them bound; its group is connectivity column 2. Group ids may come in any order; a group without elements
+ * reports 13 zeros; quasistatic groups are reported like any other (the record describes the state, not the integrator). */
+int mistark_inertia_budget(mistark_ctx* ctx, int potential, const double about[3], int32_t n_groups, double* out);
+/* out[b][13], b < n_bodies: the record of every rigid body. Arguments: array ids of t0 [3], q0 [4], v1 [3], w1 [3], mass [1] and J_loc [9, row-major, body
+ * frame] per body; the time step and gravity are those the inertia potentials have bound. t1 = t0 + dt v1, q1 = normalize(q0 + dt/2 (0, w1) q0) as in every
+ * rigid-body potential, J1 = R(q1) J_loc R(q1)^T; the item count is 1. */
+int mistark_rigid_budget(mistark_ctx* ctx, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3], double* out);
+
 /* ---- projection + assembly ------------------------------------------------------------------------------------------ */
 /* ElementHessians::project_to_PD_inplace__all / project_to_PD_for_update__selectively (ElementHessians.cpp:48-67,79-182;
  * project_to_PD.cpp:12-32). active_blocks: NULL = all elements, else ndofs/3 flags; only not-yet-projected elements
@@ -395,7 +416,8 @@ int mistark_sync(mistark_ctx* ctx);
  * "llt_panels" / "llt_fronts" (the last DirectLLT solve: 0 dense, 1 band, 2 multifrontal, -1 none yet; block rows per panel — multifrontal: of the
  * largest front —, panels, fronts), "force_readouts" (force readout calls that launched) / "force_long_rows" (block rows of the last readout
  * that were summed by a whole wavefront: more than 256 contributions), "stress_readouts" / "stress_long_rows" (the same two for the stress readout:
- * calls that launched, rows of the last nodal readout summed by a whole wavefront). */
+ * calls that launched, rows of the last nodal readout summed by a whole wavefront), "budget_readouts" / "budget_chunks" (budget readout calls that
+ * launched, chunks of the element list the last inertia budget was summed in). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

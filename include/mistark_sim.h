@@ -228,6 +228,18 @@ int mistark_sim_record_stress(mistark_sim* sim, int enabled);
 int mistark_sim_get_stress(mistark_sim* sim, int kind, double* elem_out, int64_t* n_elem);
 /* points_out [n_points x 10]: the nodal averages at the points' rows (points no element of the kind touches: ten zeros) */
 int mistark_sim_get_nodal_stress(mistark_sim* sim, int kind, double* points_out);
+/* Budget recording (off by default; not in the reference), at the same place inside the step, after the Newton callbacks that precede an evaluation:
+ * one mistark_energies over all potentials that are not user-defined, one mistark_inertia_budget per EnergyLumpedInertia potential and one
+ * mistark_rigid_budget if there are bodies (mistark.h "budget readout": records of 13 doubles, angular momentum about `about`, NULL = the origin). Results
+ * stay on the device until they are asked for. With recording off nothing is registered, launched or allocated; switching it re-registers the scene
+ * (the bodies' local inertia tensors are an engine array only while recording is on). */
+int mistark_sim_record_budget(mistark_sim* sim, int enabled, const double about[3]);
+/* The budget of the last accepted step. Every output is nullable; a first call with the buffers NULL gives the sizes. names / labels: the registry names
+ * of the potentials / the labels of the objects (of the preset that created it; empty for an inertia group or a body added directly), each followed by '\n',
+ * NUL-terminated, names_bytes / labels_bytes long. energies [n_potentials]; kinds [n_objects]: 0 deformable (an inertia group), 1 rigid body;
+ * records [n_objects x 13]; inertia groups in group order, then bodies. time: the simulation time of the accepted step. */
+int mistark_sim_get_budget(mistark_sim* sim, int32_t* n_potentials, int32_t* n_objects, int64_t* names_bytes, int64_t* labels_bytes, double* time, char* names,
+                           double* energies, char* labels, int32_t* kinds, double* records);
 /* The part of a time step before the Newton solve (Stark.cpp:145-156: before_time_step callbacks = friction tables at the start-of-step
  * geometry, rigid-body caches, v1 = 0) and the Newton callback that precedes every evaluation (contact tables at the current DoFs), as
  * separate calls: what the reference's harness does to take a stage snapshot at a given state (callbacks->run_before_time_step();

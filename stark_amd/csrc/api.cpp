@@ -579,6 +579,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "force_long_rows") *out = force_long_rows(c);
     else if (n == "stress_readouts") *out = c.n_stress_readouts;
     else if (n == "stress_long_rows") *out = stress_long_rows(c);
+    else if (n == "budget_readouts") *out = c.n_budget_readouts;
+    else if (n == "budget_chunks") *out = c.n_budget_chunks;
     else if (n == "llt_path") *out = c.llt_last_path;
     else if (n == "llt_panel_rows") *out = c.llt_last_panel_rows;
     else if (n == "llt_panels") *out = c.llt_last_panels;
@@ -730,6 +732,26 @@ int mistark_nodal_stress(mistark_ctx* ctx, const int32_t* potentials, int32_t n,
 {
     API_BEGIN
     stress_nodal_host(ctx->c, potentials, n, out_host);
+    API_END(0)
+}
+
+// ---- budget readout (budget.hip) ---------------------------------------------------------------------------------------
+int mistark_energies(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out)
+{
+    API_BEGIN
+    budget_energies(ctx->c, potentials, n, out, -1);
+    API_END(0)
+}
+int mistark_inertia_budget(mistark_ctx* ctx, int potential, const double about[3], int32_t n_groups, double* out)
+{
+    API_BEGIN
+    budget_inertia(ctx->c, potential, about, n_groups, out, -1);
+    API_END(0)
+}
+int mistark_rigid_budget(mistark_ctx* ctx, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3], double* out)
+{
+    API_BEGIN
+    budget_rigid(ctx->c, t0, q0, v1, w1, mass, J_loc, n_bodies, about, out, -1);
     API_END(0)
 }
 
@@ -1416,6 +1438,42 @@ int stress_fetch_nodal(mistark_ctx* ctx, int kind, double* out, int64_t n_rows)
 {
     API_BEGIN
     mistark::stress_fetch_nodal(ctx->c, kind, out, n_rows);
+    API_END(0)
+}
+int budget_record_energies(mistark_ctx* ctx, int slot, const std::vector<int32_t>& pots)
+{
+    API_BEGIN
+    if (pots.empty()) throw Error("budget readout: no potential to record");
+    budget_energies(ctx->c, pots.data(), (int32_t)pots.size(), nullptr, slot);
+    API_END(0)
+}
+int budget_record_inertia(mistark_ctx* ctx, int slot, int potential, const double about[3], int32_t n_groups)
+{
+    API_BEGIN
+    budget_inertia(ctx->c, potential, about, n_groups, nullptr, slot);
+    API_END(0)
+}
+int budget_record_rigid(mistark_ctx* ctx, int slot, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3])
+{
+    API_BEGIN
+    budget_rigid(ctx->c, t0, q0, v1, w1, mass, J_loc, n_bodies, about, nullptr, slot);
+    API_END(0)
+}
+int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n)
+{
+    API_BEGIN
+    budget_fetch_slot(ctx->c, slot, out, n);
+    API_END(0)
+}
+int potential_names(mistark_ctx* ctx, std::vector<std::string>& names, std::vector<char>& custom)
+{
+    API_BEGIN
+    names.clear();
+    custom.clear();
+    for (const Potential& P : ctx->c.pots) {
+        names.push_back(P.name);
+        custom.push_back(P.kind == KIND_CUSTOM);
+    }
     API_END(0)
 }
 }  // namespace mistark

@@ -556,6 +556,31 @@ struct Context
     int64_t n_stress_readouts = 0;  // counter "stress_readouts": readout calls that launched
     bool sr_stat_valid = false;
 
+    // Budget readout (budget.hip): a pipeline beside eval() like the two above, with buffers of its own. Energies: element energies of one potential
+    // at a time -> bg_elemE, a fixed-order sum -> bg_E[potential]. Inertia budget: the elements listed per group (bg_items, stable) and cut into chunks
+    // of BUDGET_CHUNK items (bg_chunks), one workgroup per chunk -> bg_partial [chunk][13], one workgroup per group folds its chunks -> bg_out [group][13].
+    DevBuf<double> bg_elemE, bg_E, bg_partial, bg_out;
+    DevBuf<uint32_t> bg_items;       // element ids, group by group, list order kept inside a group
+    DevBuf<int32_t> bg_chunks;       // per chunk: first item, item count; then per group (+1): first chunk
+    struct BudgetPlan                // what bg_items / bg_chunks hold
+    {
+        int pot = -1;
+        uint64_t conn_version = 0;
+        int n_elem = -1, n_groups = -1;
+        int64_t n_chunks = 0;
+    } bg_plan;
+    struct BudgetSlot                // what the host mirror records inside a time step and keeps on the device
+    {
+        DevBuf<double> v;
+        int64_t n = -1;              // doubles recorded (-1: nothing yet)
+        bool zero = false;           // nothing to sum: no launch, the record is zero
+    };
+    std::vector<BudgetSlot> budget_slots;
+    DevBuf<int32_t> bg_echunks;      // energies: per chunk of bg_elemE first element, element count; then per listed potential (+1): first chunk
+    std::vector<int32_t> bg_echunks_host;  // ... as last uploaded
+    int64_t n_budget_readouts = 0;  // counter "budget_readouts": readout calls that launched
+    int64_t n_budget_chunks = 0;    // counter "budget_chunks": chunks of the last inertia budget
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -660,6 +685,16 @@ int64_t stress_long_rows(Context& c);  // counter "stress_long_rows"
 void stress_record_kind(Context& c, int kind);  // every potential of the kind, id ascending: element records and nodal averages into Context::stress_slots[kind]
 void stress_fetch_elements(Context& c, int kind, double* out, int64_t* n_elem);
 void stress_fetch_nodal(Context& c, int kind, double* out, int64_t n_rows);
+// forces.hip: the refusals every readout over a list of potentials shares (registration-only and sharded contexts, bad and duplicate ids, user-defined
+// potentials), then prepare(); returns the ids in the caller's order (all = every potential)
+std::vector<int> select_potentials(Context& c, const int32_t* pots, int32_t n, bool all, const char* who);
+// Budget readout. kernels.hip: the energy-only kernel of P's kind with its element energies redirected to `scratchE`; on c.stream.
+void launch_energy_elements(Context& c, const Potential& P, double* scratchE);
+// budget.hip (records as budget.hpp lays them out). A null host pointer leaves the result on the device: slot >= 0 names the host mirror's slot.
+void budget_energies(Context& c, const int32_t* pots, int32_t n, double* out_host, int slot);
+void budget_inertia(Context& c, int pot, const double* about, int32_t n_groups, double* out_host, int slot);
+void budget_rigid(Context& c, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double* about, double* out_host, int slot);
+void budget_fetch_slot(Context& c, int slot, double* out_host, int64_t n);
 int find_kind(const char* name);
 int kind_nb(int kind);
 int kind_nbind(int kind);

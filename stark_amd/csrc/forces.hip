@@ -109,16 +109,9 @@ __global__ __launch_bounds__(BLOCK) void k_force_resultant(const double* __restr
     }
 }
 
-namespace {
-struct Selection
-{
-    std::vector<int> pots;           // selected potentials with elements, in the caller's order
-    std::vector<ForceDesc> descs;
-    std::vector<int64_t> g_off;
-    int64_t total = 0;               // contributions (element, block)
-};
-// refusals, prepare(), the selection and its layout in the readout pool
-Selection select(Context& c, const int32_t* pots, int32_t n, bool all, const char* who)
+// refusals and prepare() of every readout that takes a list of potentials (this one and budget.hip): the ids in the caller's order, all of them when
+// `all` is set
+std::vector<int> select_potentials(Context& c, const int32_t* pots, int32_t n, bool all, const char* who)
 {
     if (c.dry) throw Error(std::string(who) + ": registration-only context (mistark_create_dry): nothing can be evaluated");
     if (c.world > 1) throw Error(std::string(who) + ": single-rank accessor (a sharded context holds the elements touching its rows)");
@@ -140,6 +133,21 @@ Selection select(Context& c, const int32_t* pots, int32_t n, bool all, const cha
         if (c.pots[(size_t)p].kind == KIND_CUSTOM)
             throw Error(std::string(who) + ": potential '" + c.pots[(size_t)p].name + "' is user-defined (mistark_potential_custom): its kernels have no pool path");
     prepare(c);  // (as eval(): contact tables then have their device connectivity and current row counts; no search runs)
+    return ids;
+}
+
+namespace {
+struct Selection
+{
+    std::vector<int> pots;           // selected potentials with elements, in the caller's order
+    std::vector<ForceDesc> descs;
+    std::vector<int64_t> g_off;
+    int64_t total = 0;               // contributions (element, block)
+};
+// the selection and its layout in the readout pool
+Selection select(Context& c, const int32_t* pots, int32_t n, bool all, const char* who)
+{
+    const std::vector<int> ids = select_potentials(c, pots, n, all, who);
     Selection S;
     for (int p : ids) {
         const Potential& P = c.pots[(size_t)p];

@@ -21,5 +21,14 @@ int stress_record(mistark_ctx* ctx, int kind);
 int stress_fetch(mistark_ctx* ctx, int kind, double* out, int64_t* n_elem);
 // out[n_rows][10] of the kind's slot, n_rows = block rows of the DoF vector
 int stress_fetch_nodal(mistark_ctx* ctx, int kind, double* out, int64_t n_rows);
+// budget readout (budget.hip) into device slot `slot`: the energies of the listed potentials (one double each), the 13-double records of an
+// EnergyLumpedInertia potential's groups, of the rigid bodies (array ids as mistark_rigid_budget takes them)
+int budget_record_energies(mistark_ctx* ctx, int slot, const std::vector<int32_t>& pots);
+int budget_record_inertia(mistark_ctx* ctx, int slot, int potential, const double about[3], int32_t n_groups);
+int budget_record_rigid(mistark_ctx* ctx, int slot, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3]);
+// out[n] of slot `slot`
+int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n);
+// registry name of every potential in id order, and whether it is user-defined
+int potential_names(mistark_ctx* ctx, std::vector<std::string>& names, std::vector<char>& custom);
 
 }  // namespace mistark

@@ -422,6 +422,7 @@ Line::Handler DeformablesPresets::add_line(const std::string& label, const std::
 {
     PointSetHandler ps = deformables->point_sets->add(V, label);
     auto inertia = deformables->lumped_inertia->add(ps, segments, p.inertia);
+    deformables->lumped_inertia->set_label(inertia, label);
     auto seg = deformables->segment_strain;
     const size_t pos = p.strain.elasticity_only ? seg->n_elasticity_only() : seg->n_complete();  // (cells and elements are both `segments`, in order)
     auto strain = seg->add(ps, segments, p.strain);

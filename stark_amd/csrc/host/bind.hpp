@@ -17,9 +17,11 @@ struct BindList
     }
     void add_id(int id, int stride, int col) { b.push_back({id, stride, col}); }
     template <std::size_t N>
-    void potential(const char* name, const std::vector<std::array<int32_t, N>>& conn)
+    int potential(const char* name, const std::vector<std::array<int32_t, N>>& conn)
     {
-        stark.check(mistark_potential(ctx, name, conn.empty() ? nullptr : conn[0].data(), (int32_t)conn.size(), (int32_t)N, b.data(), (int32_t)b.size()));
+        const int id = mistark_potential(ctx, name, conn.empty() ? nullptr : conn[0].data(), (int32_t)conn.size(), (int32_t)N, b.data(), (int32_t)b.size());
+        stark.check(id);
+        return id;
     }
 };
 }  // namespace mistark

@@ -132,6 +132,7 @@ void EnergyRigidBodyInertia::add(int rb_idx, double m, const Mat3& inertia_loc)
     mass.push_back(m);
     J_loc.push_back(inertia_loc);
     J0_glob.push_back(inertia_loc);
+    labels.push_back("");
     linear_damping.push_back(0.0);
     angular_damping.push_back(0.0);
     is_quasistatic.push_back(0.0);
@@ -139,7 +140,7 @@ void EnergyRigidBodyInertia::add(int rb_idx, double m, const Mat3& inertia_loc)
 }
 void EnergyRigidBodyInertia::register_potentials(mistark_ctx* ctx)
 {
-    id_J0 = -1;
+    id_J0 = id_mass = id_J_loc = -1;
     if (conn.empty()) return;
     const int64_t n = (int64_t)mass.size();
     {
@@ -149,7 +150,7 @@ void EnergyRigidBodyInertia::register_potentials(mistark_ctx* ctx)
         B.add_id(rb->id_v0, 3, 0);
         B.add_id(rb->id_a, 3, 0);
         B.add_id(rb->id_force, 3, 0);
-        B.add(mass.data(), n, 1, 0);
+        id_mass = B.add(mass.data(), n, 1, 0);
         B.add(linear_damping.data(), n, 1, 0);
         B.add(is_quasistatic.data(), n, 1, 0);
         B.add_id(stark.dt_array(), 1, -1);
@@ -168,6 +169,11 @@ void EnergyRigidBodyInertia::register_potentials(mistark_ctx* ctx)
         B.add(is_quasistatic.data(), n, 1, 0);
         B.add_id(stark.dt_array(), 1, -1);
         B.potential("EnergyRigidBodyInertia_Angular", conn);
+    }
+    if (stark.budget_recording) {
+        // budget recording: the rigid budget reads J_loc on the device (bound by no potential: registered only while recording is on)
+        stark.check(id_J_loc = mistark_array(ctx, J_loc[0].data(), n, 9));
+        stark.budget_rigid_source = {rb->id_t0, rb->id_q0_, rb->id_v1, rb->id_w1, id_mass, id_J_loc, (int)n, &labels};
     }
 }
 void EnergyRigidBodyInertia::_before_time_step()

@@ -55,6 +55,9 @@ void Stark::ensure_registered()
     force_n_points = force_n_rb = 0;
     forces_recorded = false;  // (recorded vectors live in the context just replaced)
     stress_recorded = false;
+    budget_recorded = false;
+    budget_inertia_sources.clear();
+    budget_rigid_source = BudgetRigidSource{};
     for (auto* m : models) m->register_dofs(ctx);
     dt_array_id = mistark_array(ctx, &dt, 1, 1);
     check(dt_array_id);
@@ -195,6 +198,27 @@ bool Stark::run_one_step()
             for (int kind = 0; kind < 3; kind++) check(stress_record(ctx, kind));
             stress_recorded = true;
         }
+        if (budget_recording) {
+            for (auto& f : n.before_energy_evaluation) f();  // (as force recording: at an unchanged state answered from the installed tables)
+            std::vector<std::string> names;
+            std::vector<char> custom;
+            check(potential_names(ctx, names, custom));
+            budget_pots.clear();
+            budget_names.clear();
+            for (size_t p = 0; p < names.size(); p++)
+                if (!custom[p]) {
+                    budget_pots.push_back((int32_t)p);
+                    budget_names.push_back(names[p]);
+                }
+            int slot = 0;
+            if (!budget_pots.empty()) check(budget_record_energies(ctx, slot, budget_pots));
+            slot++;
+            for (const BudgetInertiaSource& src : budget_inertia_sources) check(budget_record_inertia(ctx, slot++, src.potential, budget_about.data(), src.n_groups));
+            const BudgetRigidSource& r = budget_rigid_source;
+            if (r.n > 0) check(budget_record_rigid(ctx, slot, r.t0, r.q0, r.v1, r.w1, r.mass, r.J_loc, r.n, budget_about.data()));
+            budget_time = current_time + dt;
+            budget_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -281,6 +305,40 @@ void Stark::get_nodal_stress(int kind, double* points_out)
     const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
     if (r0 < 0) throw std::runtime_error("get_nodal_stress: the point set has no DoFs");
     std::copy(all.begin() + 10 * r0, all.begin() + 10 * (r0 + force_n_points), points_out);
+}
+void Stark::record_budget(bool enabled, const Vec3& about)
+{
+    if (enabled != budget_recording) registration_dirty = true;  // (the bodies' J_loc is registered only while recording is on)
+    budget_recording = enabled;
+    budget_about = about;
+    budget_recorded = false;
+}
+void Stark::get_budget(BudgetReport& out)
+{
+    if (!budget_recording) throw std::runtime_error("get_budget: budget recording is off (record_budget)");
+    if (!ctx || !budget_recorded) throw std::runtime_error("get_budget: no time step has been accepted since recording was switched on");
+    out = BudgetReport{};
+    out.time = budget_time;
+    int slot = 0;
+    if (!budget_pots.empty()) {
+        std::vector<double> E(budget_pots.size());
+        check(budget_fetch(ctx, slot, E.data(), (int64_t)E.size()));
+        for (size_t k = 0; k < E.size(); k++) out.potentials.push_back({budget_names[k], E[k]});
+    }
+    slot++;
+    auto fetch_records = [&](int n, int kind, const std::vector<std::string>* labels) {
+        std::vector<double> rec((size_t)13 * n);
+        check(budget_fetch(ctx, slot++, rec.data(), (int64_t)rec.size()));
+        for (int g = 0; g < n; g++) {
+            BudgetObject o;
+            o.label = labels && (size_t)g < labels->size() ? (*labels)[(size_t)g] : "";
+            o.kind = kind;
+            std::copy(rec.begin() + 13 * g, rec.begin() + 13 * (g + 1), o.rec.begin());
+            out.objects.push_back(o);
+        }
+    };
+    for (const BudgetInertiaSource& src : budget_inertia_sources) fetch_records(src.n_groups, 0, src.labels);
+    if (budget_rigid_source.n > 0) fetch_records(budget_rigid_source.n, 1, budget_rigid_source.labels);
 }
 std::string Stark::get_frame_path(const std::string& name) const
 {
@@ -458,11 +516,13 @@ void EnergyLumpedInertia::register_potentials(mistark_ctx* ctx)
     B.add(is_quasistatic.data(), (int64_t)is_quasistatic.size(), 1, 2);
     B.add_id(stark.dt_array(), 1, -1);
     B.add_id(stark.gravity_array(), 3, -1);
-    B.potential("EnergyLumpedInertia", conn);
+    const int pot = B.potential("EnergyLumpedInertia", conn);
+    stark.budget_inertia_sources.push_back({pot, (int)density.size(), &group_labels});
 }
 EnergyLumpedInertia::Handler EnergyLumpedInertia::add(const PointSetHandler& set, const std::vector<int>& points, const std::vector<double>& vol, const Params& params)
 {
     const int group = (int)density.size();
+    group_labels.push_back("");
     density.push_back(params.density);
     damping.push_back(params.damping);
     is_quasistatic.push_back(params.quasistatic ? 1.0 : 0.0);
@@ -946,6 +1006,7 @@ Surface::Handler DeformablesPresets::add_surface(const std::string& label, const
     // DeformablesPresets.cpp:31-44
     PointSetHandler ps = deformables->point_sets->add(V, label);
     auto inertia = deformables->lumped_inertia->add(ps, T, p.inertia);
+    deformables->lumped_inertia->set_label(inertia, label);
     auto tri = deformables->triangle_strain;
     const size_t pos = p.strain.elasticity_only ? tri->n_elasticity_only() : tri->n_complete();  // (cells and elements are both T, in order)
     auto strain = tri->add(ps, T, p.strain);
@@ -970,6 +1031,7 @@ Volume::Handler DeformablesPresets::add_volume(const std::string& label, const s
     // DeformablesPresets.cpp:65-79: the collision mesh is the surface of the tet mesh
     PointSetHandler ps = deformables->point_sets->add(V, label);
     auto inertia = deformables->lumped_inertia->add(ps, T, p.inertia);
+    deformables->lumped_inertia->set_label(inertia, label);
     auto tet = deformables->tet_strain;
     const size_t pos = p.strain.elasticity_only ? tet->n_elasticity_only() : tet->n_complete();  // (the potential's elements are T, in order)
     auto strain = tet->add(ps, T, p.strain);
@@ -1018,6 +1080,7 @@ RigidBody::Handler RigidBodyPresets::add(const std::string& label, double mass, 
 {
     // RigidBodyPresets.cpp:11-26
     RigidBodyHandler body = rigidbodies->add(mass, inertia_local);
+    rigidbodies->inertia->labels[(size_t)body.get_idx()] = label;
     ContactHandler contact;
     if (interactions->contact->is_active()) contact = interactions->contact->add_triangles(body, V, T, cp);
     if (!label.empty() && interactions->output) interactions->output->add_triangle_mesh(label, body, V, T);

@@ -150,6 +150,39 @@ public:
     void get_stress(int kind, double* elem_out /* n_elem x 16, nullable */, int64_t* n_elem);
     void get_nodal_stress(int kind, double* points_out /* n_points x 10 */);
     bool stress_recording = false, stress_recorded = false;
+    // Budget recording (off by default; not in the reference): at the same place, after the before_energy_evaluation callbacks, one mistark_energies over
+    // all potentials that are not user-defined, one inertia budget per EnergyLumpedInertia potential and one rigid budget if there are bodies
+    // (include/mistark.h "budget readout"); kept on the device until get_budget() downloads them. Off: nothing is registered, launched or allocated.
+    // Switching it re-registers (the bodies' J_loc is an engine array only while recording is on).
+    struct BudgetObject
+    {
+        std::string label;  // of the preset that created it ("" for an inertia group added directly)
+        int kind = 0;       // 0 deformable (an inertia group), 1 rigid body
+        std::array<double, 13> rec{};
+    };
+    struct BudgetReport
+    {
+        std::vector<std::pair<std::string, double>> potentials;  // registry name, energy; in potential order
+        std::vector<BudgetObject> objects;                       // inertia groups in group order, then bodies
+        double time = 0.0;                                       // simulation time of the accepted step
+    };
+    void record_budget(bool enabled, const Vec3& about = {0.0, 0.0, 0.0});
+    void get_budget(BudgetReport& out);
+    bool budget_recording = false, budget_recorded = false;
+    // what the models note while they register: the inertia potentials (id, groups, their labels) and the bodies' arrays
+    struct BudgetInertiaSource
+    {
+        int potential = -1;
+        int n_groups = 0;
+        const std::vector<std::string>* labels = nullptr;
+    };
+    struct BudgetRigidSource
+    {
+        int t0 = -1, q0 = -1, v1 = -1, w1 = -1, mass = -1, J_loc = -1, n = 0;
+        const std::vector<std::string>* labels = nullptr;
+    };
+    std::vector<BudgetInertiaSource> budget_inertia_sources;
+    BudgetRigidSource budget_rigid_source;
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -163,6 +196,10 @@ private:
     bool force_recording = false;
     std::vector<std::string> force_groups;
     bool forces_recorded = false;  // ... in the current engine context
+    Vec3 budget_about = {0.0, 0.0, 0.0};
+    double budget_time = 0.0;
+    std::vector<int32_t> budget_pots;       // the potentials of slot 0, as recorded
+    std::vector<std::string> budget_names;  // ... and their names
     void _initialize();
     void _write_frame();
 };
@@ -265,11 +302,13 @@ public:
     Params get_params(const Handler& h) const;
     void set_params(const Handler& h, const Params& p);
     double get_mass(const Handler& h) const;
+    void set_label(const Handler& h, const std::string& label) { group_labels[(size_t)h.idx] = label; }  // the presets name their group (budget readout)
     void register_potentials(mistark_ctx* ctx) override;
 
 private:
     Stark& stark;
     spPointDynamics dyn;
+    std::vector<std::string> group_labels;     // per group: "" unless a preset named it
     std::vector<std::array<int32_t, 3>> conn;  // idx, glob, group
     std::vector<double> density, damping, is_quasistatic, lumped_volume;
     bool params_dirty = true;
@@ -454,6 +493,7 @@ class EnergyRigidBodyInertia : public Registrable
 public:
     std::vector<double> mass, linear_damping, angular_damping, is_quasistatic;
     std::vector<Mat3> J_loc, J0_glob;
+    std::vector<std::string> labels;  // per body: "" unless a preset named it (budget readout)
     EnergyRigidBodyInertia(Stark& stark, spRigidBodyDynamics rb);
     void add(int rb_idx, double mass, const Mat3& inertia_loc);
     void register_potentials(mistark_ctx* ctx) override;
@@ -462,7 +502,7 @@ private:
     Stark& stark;
     spRigidBodyDynamics rb;
     std::vector<std::array<int32_t, 1>> conn;
-    int id_J0 = -1;
+    int id_J0 = -1, id_mass = -1, id_J_loc = -1;
     void _before_time_step();
 };
 

@@ -767,6 +767,36 @@ int mistark_sim_get_nodal_stress(mistark_sim* s, int kind, double* points_out)
     s->sim->get_stark().get_nodal_stress(kind, points_out);
     SIM_END
 }
+int mistark_sim_record_budget(mistark_sim* s, int enabled, const double about[3])
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_budget(enabled != 0, about ? Vec3{about[0], about[1], about[2]} : Vec3{0.0, 0.0, 0.0});
+    SIM_END
+}
+int mistark_sim_get_budget(mistark_sim* s, int32_t* n_potentials, int32_t* n_objects, int64_t* names_bytes, int64_t* labels_bytes, double* time, char* names, double* energies,
+                           char* labels, int32_t* kinds, double* records)
+{
+    SIM_BEGIN
+    Stark::BudgetReport r;
+    s->sim->get_stark().get_budget(r);
+    std::string nm, lb;
+    for (const auto& p : r.potentials) nm += p.first + "\n";
+    for (const auto& o : r.objects) lb += o.label + "\n";
+    if (n_potentials) *n_potentials = (int32_t)r.potentials.size();
+    if (n_objects) *n_objects = (int32_t)r.objects.size();
+    if (names_bytes) *names_bytes = (int64_t)nm.size() + 1;
+    if (labels_bytes) *labels_bytes = (int64_t)lb.size() + 1;
+    if (time) *time = r.time;
+    if (names) std::memcpy(names, nm.c_str(), nm.size() + 1);
+    if (labels) std::memcpy(labels, lb.c_str(), lb.size() + 1);
+    for (size_t k = 0; k < r.potentials.size(); k++)
+        if (energies) energies[k] = r.potentials[k].second;
+    for (size_t k = 0; k < r.objects.size(); k++) {
+        if (kinds) kinds[k] = r.objects[k].kind;
+        if (records) std::copy(r.objects[k].rec.begin(), r.objects[k].rec.end(), records + 13 * k);
+    }
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

@@ -897,6 +897,23 @@ void launch_force_elements(Context& c, const Potential& P, double* pool, double*
     throw Error("unknown potential kind");
 }
 
+// Budget readout (budget.hip): the energy-only kernel on a copy of the potential's argument block, element energies to `scratchE` (zeros for
+// elements switched off). Nothing eval() owns is written.
+void launch_energy_elements(Context& c, const Potential& P, double* scratchE)
+{
+    if (P.kind == KIND_CUSTOM) throw Error("budget readout: potential '" + P.name + "' is user-defined");
+    if (P.args.e_count == 0) return;
+    if (P.args.elem_list || P.args.e_count != P.n_elem) throw Error("budget readout: single-rank accessor");
+    const PotArgs A = P.args;
+    int k = 0;
+#define X(En)                                                                                                                        \
+    if (P.kind == k) { hipLaunchKernelGGL((k_eval_p<En>), dim3(grid_for(A.e_count)), dim3(BLOCK), 0, c.stream, A, scratchE); return; } \
+    k++;
+    MISTARK_FOR_EACH_ENERGY(X)
+#undef X
+    throw Error("unknown potential kind");
+}
+
 // a contact / friction table that eval() may put into the shared launch (k_eval_pgh_multi): generic kernel, Hessian wanted; *np = lanes per row
 static bool joins_multi_pgh(const Context& c, const Potential& P, int* np)
 {

@@ -310,6 +310,38 @@ class Engine:
         self._ck(self.L.mistark_nodal_stress(self.h, ptr, ids.size, out.ctypes.data))
         return out
 
+    # ---- budget readout (include/mistark.h "budget readout") ----------------------------------------------------------------
+    def energies(self, pots=None) -> np.ndarray:
+        """The energy of each listed potential id at the current DoFs (None or empty: of every potential, in id order); bit-reproducible."""
+        ids, ptr = self._pot_list(pots)
+        n = ids.size if ids.size else len(self.describe_potentials())
+        out = np.zeros(n)
+        self._ck(self.L.mistark_energies(self.h, ptr, ids.size, out.ctypes.data if n else None))
+        return out
+
+    def describe_potentials(self):
+        import json
+        n = self.L.mistark_describe(self.h, None, 0)
+        buf = C.create_string_buffer(int(n))
+        self.L.mistark_describe(self.h, buf, n)
+        return json.loads(buf.value.decode())["potentials"]
+
+    def inertia_budget(self, pot: int, n_groups: int, about=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """records [n_groups, 13] of an EnergyLumpedInertia potential: mass, first moment, momentum, angular momentum about `about`, kinetic and
+        gravitational energy, item count per group (connectivity column 2)."""
+        ab = np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        out = np.zeros((int(n_groups), 13))
+        self._ck(self.L.mistark_inertia_budget(self.h, int(pot), ab.ctypes.data, int(n_groups), out.ctypes.data if out.size else None))
+        return out
+
+    def rigid_budget(self, t0, q0, v1, w1, mass, J_loc, n_bodies: int, about=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """records [n_bodies, 13] of the rigid bodies whose state arrays have the given ids (J_loc: 9 doubles per body, row-major, body frame)."""
+        ab = np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        out = np.zeros((int(n_bodies), 13))
+        self._ck(self.L.mistark_rigid_budget(self.h, int(t0), int(q0), int(v1), int(w1), int(mass), int(J_loc), int(n_bodies), ab.ctypes.data,
+                                             out.ctypes.data if out.size else None))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)

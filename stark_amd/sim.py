@@ -136,6 +136,9 @@ def _lib():
         L.mistark_sim_record_stress.argtypes = [p, C.c_int]
         L.mistark_sim_get_stress.argtypes = [p, C.c_int, p, C.POINTER(C.c_int64)]
         L.mistark_sim_get_nodal_stress.argtypes = [p, C.c_int, p]
+        L.mistark_sim_record_budget.argtypes = [p, C.c_int, D]
+        I32 = C.POINTER(C.c_int32)
+        L.mistark_sim_get_budget.argtypes = [p, I32, I32, I64, I64, D, p, p, p, p, p]
         _bound = True
     return L
 
@@ -512,6 +515,39 @@ class Simulation:
         if nodal.size:
             self._ck(self.L.mistark_sim_get_nodal_stress(self.h, int(kind), nodal.ctypes.data))
         return rec, nodal
+
+    # ---- budget recording --------------------------------------------------------------------------------------------------
+    def record_budget(self, on=True, about=(0.0, 0.0, 0.0)):
+        """Every accepted step then keeps the energy of every potential and the mass, momentum and energy record of every object (inertia group,
+        rigid body) of the state it converged at, on the device; angular momentum about `about`."""
+        ab = (C.c_double * 3)(*[float(v) for v in about])
+        self._ck(self.L.mistark_sim_record_budget(self.h, int(bool(on)), ab))
+
+    def budget(self):
+        """The budget of the last accepted step: dict(potentials={registry name: energy}, objects=[dict(label, kind, mass, com, momentum,
+        angular_momentum, kinetic, gravitational, count)], total=dict(the sums over the objects), time). kinetic + gravitational + the strain potentials'
+        entries is a mechanical energy; EnergyLumpedInertia's own entry is the incremental potential."""
+        npot, nobj, nb, lb, t = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self.L.mistark_sim_get_budget(self.h, C.byref(npot), C.byref(nobj), C.byref(nb), C.byref(lb), C.byref(t), None, None, None, None, None))
+        names, labels = C.create_string_buffer(nb.value), C.create_string_buffer(lb.value)
+        E = np.zeros(npot.value)
+        kinds = np.zeros(nobj.value, dtype=np.int32)
+        rec = np.zeros((nobj.value, 13))
+        self._ck(self.L.mistark_sim_get_budget(self.h, C.byref(npot), C.byref(nobj), C.byref(nb), C.byref(lb), C.byref(t), names, E.ctypes.data if E.size else None, labels,
+                                               kinds.ctypes.data if kinds.size else None, rec.ctypes.data if rec.size else None))
+        potentials = {}
+        for name, e in zip(names.value.decode().split("\n")[:-1], E):
+            potentials[name] = potentials.get(name, 0.0) + float(e)
+        objects = []
+        for label, kind, r in zip(labels.value.decode().split("\n")[:-1], kinds, rec):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                com = r[1:4] / r[0] if r[0] != 0.0 else np.full(3, np.nan)
+            objects.append(dict(label=label, kind="rigid" if kind == 1 else "deformable", mass=float(r[0]), com=com, momentum=r[4:7].copy(),
+                                angular_momentum=r[7:10].copy(), kinetic=float(r[10]), gravitational=float(r[11]), count=int(r[12])))
+        total = dict(mass=sum(o["mass"] for o in objects), momentum=sum((o["momentum"] for o in objects), np.zeros(3)),
+                     angular_momentum=sum((o["angular_momentum"] for o in objects), np.zeros(3)), kinetic=sum(o["kinetic"] for o in objects),
+                     gravitational=sum(o["gravitational"] for o in objects))
+        return dict(potentials=potentials, objects=objects, total=total, time=t.value)
 
     def engine_handle(self):
         return C.c_void_p(self.L.mistark_sim_engine(self.h))
