@@ -76,6 +76,53 @@ int mistark_contact_get_table(mistark_ctx* ctx, const char* potential, int32_t* 
 int mistark_contact_get_friction_data(mistark_ctx* ctx, const char* potential, double* T, double* mu, double* fn, double* bary, int32_t* nbary);
 /* Parity access: collision vertex positions used by the last update [n_collision_vertices x 3]. */
 int mistark_contact_get_vertices(mistark_ctx* ctx, double* x, int64_t* n_vertices);
+
+/* ---- contact report (opt-in, not in the reference) -------------------------------------------------------------------------
+ * What the contact itself looks like at the current DoFs: which primitives are in contact, how close, where the closest points and the normal lie, how
+ * much normal force each pair carries and what pressure that puts on a surface. A pipeline of its own beside mistark_eval, like the force, stress and
+ * budget readouts of mistark.h: it reads the key list of the barrier tables as installed (no search runs), recomputes the collision vertices at the
+ * current DoFs (x0 + dt v1, rigid bodies as the detector moves them; dt = the bound dt array) into a buffer of its own, and writes nothing the
+ * evaluation or the solver own, and nothing of the detector's once a search has run. (Before the first search of a mesh set the collision meshes are not on
+ * the device yet: a report then uploads them as that search would — mesh arrays uploaded, the detector's position and box buffers allocated, its box cache
+ * marked stale. The size queries below do not even do that.) No floating-point atomics; every sum runs in a fixed order over the row list and through a fixed tree, so a result
+ * depends on the row order alone and two reports of one state give the same bits. It costs nothing unless it is called. All three may be called between
+ * solves and from any Newton callback. Refused, with the cause in the message: sharded contexts (single-rank accessor), registration-only contexts
+ * (mistark_create_dry), contexts without mistark_contact_init. Before the first search, after a change of the mesh set or of the collision switches
+ * that has not been searched yet, or with no pair in range: zero rows, gaps +inf, counts 0 — not an error.
+ *
+ * Rows come in key order, the order of the installed tables: the rows of table t (0..20, the order of the potentials' registration:
+ * contact_d_d_pt_pp .. contact_rb_d_ee_ep) are contiguous and correspond one to one to mistark_contact_get_table's. Roles are the key's primitives,
+ * not the A / B of the reference's tables: a = the point or the first edge, b = the triangle or the second edge. The distance is that of the closest
+ * feature the search classified (point-point, point-line, point-plane, line-line, parameters unclamped), as the table's potential evaluates it; the pair
+ * is never classified again.
+ *   rows_i [n][8]:  0 table | 1 source (0 point-triangle, 1 edge-edge) | 2 closest-feature type | 3 group of a | 4 group of b | 5 primitive a (global
+ *                   collision point / edge) | 6 primitive b (global collision triangle / edge) | 7 flags: +1 mollified (edge-edge row, mollifier < 1),
+ *                   +2 open (d >= dhat), +4 degenerate (d zero or not finite: the normal is zeros)
+ *   rows_d [n][16]: 0 d | 1 dhat = thickness[ga] + thickness[gb] | 2..4 closest point on a | 5..7 closest point on b | 8..10 unit normal (cA - cB) / d,
+ *                   from b to a | 11 mollifier m (1 for point-triangle rows) | 12 fn = m k (dhat - d)^2 [N] | 13 E = m k (dhat - d)^3 / 3 [J], unclamped
+ *                   as the potential has it | 14, 15 point-triangle: barycentrics beta1, beta2 of cB (beta0 = 1 - beta1 - beta2); edge-edge: s along a,
+ *                   t along b. Node weights: a side [1] or [1 - s, s], b side [beta0, beta1, beta2] or [1 - t, t]; vertex and edge features have
+ *                   exact 0 / 1 in the places they do not use.
+ * fn of a mollified row is the barrier part only: the force of such a row also has a b grad(m) term.
+ * Outputs are nullable: a first call with rows_i = rows_d = NULL gives n_rows from host counts alone: nothing is launched, uploaded or allocated (so do the
+ * size queries of the two calls below).
+ * Each of the three calls with an output runs the whole pipeline — positions, rows, two radix sorts, the vertex pass, the pair pass — and downloads its own
+ * part: a caller who wants all three pays for the pipeline three times (tens of microseconds of kernels each, profiles/contact_report_cost.txt). Nothing is
+ * cached between calls, because nothing the engine tracks says that DoFs, state arrays and key list are all unchanged; the host mirror's recording
+ * (mistark_sim_record_contacts) runs the pipeline once per step for all three parts.
+ * A key that names a primitive outside the meshes (a detector bug, never seen) gives a row of zeros with flag 4 that takes no part in the vertex and pair
+ * records. */
+int mistark_contact_report(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows);
+/* out [n_collision_vertices][5]: 0 gap = the smallest d over the rows whose primitive a or b contains the vertex (+inf: none) | 1 number of such rows |
+ * 2 normal force share = sum of w fn over them, w the vertex's node weight in the row (as it is: outside the feature a weight is 0, at a moved state it
+ * may leave [0, 1]) | 3 area = a third of the current areas of the vertex's collision triangles (0 for a rod vertex) | 4 pressure = [2] / [3] where
+ * [3] > 0, else 0. group [n], source_index [n]: the vertex's group and its index in the physical system's vertex array (mistark_contact_add_mesh's
+ * vertex_index), so that a caller can map collision vertices to his own. Every output is nullable. */
+int mistark_contact_vertex_report(mistark_ctx* ctx, double* out, int32_t* group, int32_t* source_index, int64_t* n_vertices);
+/* out [n_groups][n_groups][8], entries ga <= gb filled, the rest zero: 0 rows | 1 smallest d (+inf: none) | 2 dhat | 3 sum fn | 4..6 sum fn n, oriented as
+ * the force on the lower-numbered group (ga == gb: in role order, on a from b) | 7 sum E. out nullable: n_groups alone. */
+int mistark_contact_pair_report(mistark_ctx* ctx, double* out, int32_t* n_groups);
+
 /* Binding recipe of one of the 35 potentials: (role, stride, connectivity column) per binding in the reference's order;
  * roles index the members of mistark_contact_arrays (0..11), 12 = T, 13 = mu, 14 = fn, 15 = bary. Returns n_bindings. */
 int mistark_contact_recipe(const char* potential, int32_t* conn_stride, int32_t* roles, int32_t* strides, int32_t* conn_cols);

@@ -240,6 +240,18 @@ int mistark_sim_record_budget(mistark_sim* sim, int enabled, const double about[
  * records [n_objects x 13]; inertia groups in group order, then bodies. time: the simulation time of the accepted step. */
 int mistark_sim_get_budget(mistark_sim* sim, int32_t* n_potentials, int32_t* n_objects, int64_t* names_bytes, int64_t* labels_bytes, double* time, char* names,
                            double* energies, char* labels, int32_t* kinds, double* records);
+/* Contact recording (off by default; not in the reference), at the same place inside the step: one contact report of the end-of-step state
+ * (mistark_contact.h "contact report": the rows of the installed barrier tables, the vertex records, the group-pair records), after the Newton callbacks
+ * that precede an evaluation, so that the installed tables are that state's. Results stay on the device until they are asked for. With recording off
+ * nothing is launched or allocated. */
+int mistark_sim_record_contacts(mistark_sim* sim, int enabled);
+/* The contact report of the last accepted step. Every output is nullable; a first call with the buffers NULL gives the sizes. rows_i [n_rows x 8],
+ * rows_d [n_rows x 16], vertices [n_vertices x 5], vertex_group / vertex_source [n_vertices] (the collision vertex's group and its index in the vertex
+ * array of its physical system), pairs [n_groups x n_groups x 8]; labels: per group the label of the preset that created it (empty otherwise), each
+ * followed by '\n', NUL-terminated, labels_bytes long. time: the simulation time of the accepted step. A scene without contact reports empty arrays.
+ * An error while recording is off. */
+int mistark_sim_get_contacts(mistark_sim* sim, int64_t* n_rows, int64_t* n_vertices, int32_t* n_groups, int64_t* labels_bytes, double* time, int32_t* rows_i, double* rows_d,
+                             double* vertices, int32_t* vertex_group, int32_t* vertex_source, double* pairs, char* labels);
 /* The part of a time step before the Newton solve (Stark.cpp:145-156: before_time_step callbacks = friction tables at the start-of-step
  * geometry, rigid-body caches, v1 = 0) and the Newton callback that precedes every evaluation (contact tables at the current DoFs), as
  * separate calls: what the reference's harness does to take a stage snapshot at a given state (callbacks->run_before_time_step();

@@ -1842,6 +1842,52 @@ int64_t detect_and_route(Context& c, double dt, bool friction)
     lap(6);
     return n;
 }
+}  // namespace
+// ---- contact report (contact_report.hip): read access to the detector ------------------------------------------------------------------
+void contact_report_view(Context& c, ContactReportView& v, bool sizes_only)
+{
+    ContactSystem& cs = CS(c);
+    if (sizes_only) {
+        v = ContactReportView{};
+        v.n_mesh = (int)cs.meshes.size(); v.n_v = cs.n_v; v.n_t = cs.n_t; v.n_e = cs.n_e;
+        v.h_tri = &cs.h_tri; v.h_cv_src = &cs.h_cv_src; v.h_cv_mesh = &cs.h_cv_mesh;
+        v.n_keys = cs.n_prev > 0 ? cs.n_prev : 0;
+        return;
+    }
+    prepare(c);
+    // before the first search of the current mesh set the meshes are not on the device yet: what that search would do first. Afterwards the device copy is
+    // left alone even when it is marked stale (a friction coefficient set since): the keys were installed with it, and a refresh would drop the box cache
+    if (cs.n_prev < 0 || !cs.cv_src.p) upload_meshes(c, cs);
+    v = ContactReportView{};
+    v.cv_src = cs.cv_src.p; v.cv_mesh = cs.cv_mesh.p; v.tri = cs.tri.p; v.tri_mesh = cs.tri_mesh.p; v.edge = cs.edge.p; v.edge_mesh = cs.edge_mesh.p;
+    v.mesh_kind = cs.mesh_kind.p;
+    v.thick = arr_dev(c, cs.arr.thickness); v.k = arr_dev(c, cs.arr.k); v.X_rest = arr_dev(c, cs.arr.X); v.rb_xloc = arr_dev(c, cs.arr.rb_xloc);
+    v.n_mesh = (int)cs.meshes.size(); v.n_v = cs.n_v; v.n_t = cs.n_t; v.n_e = cs.n_e;
+    v.prim_bits = PRIM_BITS;
+    v.h_tri = &cs.h_tri; v.h_cv_src = &cs.h_cv_src; v.h_cv_mesh = &cs.h_cv_mesh;
+    v.keys = cs.prev.p;
+    v.n_keys = cs.n_prev > 0 ? cs.n_prev : 0;
+    int at = 0;
+    for (int t = 0; t < N_CONTACT_TABLES; t++) {
+        v.bounds[t] = at;
+        if (v.n_keys > 0 && cs.tables[t].pot >= 0) at += cs.tables[t].n;
+    }
+    v.bounds[N_CONTACT_TABLES] = at;
+    if (at != (int)v.n_keys) throw Error("contact report: the installed tables hold " + std::to_string(at) + " rows, the key list " + std::to_string(v.n_keys));
+    if (v.n_mesh > 0 && c.arrays[cs.arr.thickness].n_items < (int64_t)v.n_mesh) throw Error("contact: the thickness array must hold one value per collision mesh");
+}
+void contact_report_positions(Context& c, double* X_dev)
+{
+    ContactSystem& cs = CS(c);
+    if (cs.n_v == 0) return;
+    const Array& a = c.arrays[cs.arr.dt];
+    if (!a.host || a.n_items < 1) throw Error("contact report: the dt array has no host value");
+    const ContactDev d = dev_view(c, cs);
+    hipLaunchKernelGGL(k_contact_vertices, dim3((cs.n_v + CB - 1) / CB), dim3(CB), 0, c.stream, d, arr_dev(c, cs.arr.x0), arr_dev(c, cs.arr.v1), arr_dev(c, cs.arr.rb_xloc),
+                       arr_dev(c, cs.arr.rb_v1), arr_dev(c, cs.arr.rb_w1), arr_dev(c, cs.arr.rb_t0), arr_dev(c, cs.arr.rb_q0), a.host[0], X_dev);
+    MS_CHECK(hipGetLastError());
+}
+namespace {
 int64_t count_intersections_uncached(Context& c, double dt);
 // (the check of an accepted line-search candidate and the check of the converged state one evaluation later see the same DoFs: answered from
 // the last count while nothing the vertices depend on has changed — Context::data_version)

@@ -581,6 +581,29 @@ struct Context
     int64_t n_budget_readouts = 0;  // counter "budget_readouts": readout calls that launched
     int64_t n_budget_chunks = 0;    // counter "budget_chunks": chunks of the last inertia budget
 
+    // Contact report (contact_report.hip): the fourth pipeline beside eval(). Rows of the installed barrier-table keys at the current DoFs (cr_X: collision
+    // vertex positions of the report's own, the detector's are not written), one contribution per (row, primitive vertex) sorted by collision vertex and
+    // summed in sorted order -> per-vertex records, rows sorted by group pair (stable) and summed by one workgroup per pair -> per-pair records.
+    struct ContactReportSet          // [0]: what the accessors return, [1]: what the host mirror records inside a time step and keeps on the device
+    {
+        DevBuf<int32_t> rows_i;      // [n_rows][8]
+        DevBuf<double> rows_d;       // [n_rows][16]
+        DevBuf<double> vert;         // [n_v][5]
+        DevBuf<double> pair;         // [n_groups][n_groups][8]
+        int64_t n_rows = -1;         // -1: nothing yet
+        int64_t n_v = 0;
+        int n_groups = 0;
+    };
+    ContactReportSet cr_set[2];
+    DevBuf<double> cr_X, cr_w;       // positions [n_v][3]; weight of every contribution [4 n_rows]
+    DevBuf<uint32_t> cr_key, cr_key_alt, cr_val, cr_val_alt;
+    DevBuf<uint8_t> cr_cub_tmp;
+    DevBuf<int32_t> cr_inc;          // triangle incidence of the collision vertices: start [n_v + 1], then the triangles; built once per mesh set
+    int cr_inc_meshes = -1;          // ... for this many meshes
+    DevBuf<uint32_t> cr_stat;        // [0]: vertices of the last report summed by a whole wavefront (counter "contact_report_long_rows")
+    bool cr_stat_valid = false;
+    int64_t n_contact_reports = 0;   // counter "contact_reports": calls that launched
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -640,6 +663,31 @@ int64_t contact_searches(const Context& c, bool repeated);  // counters "contact
 int64_t contact_ccd_counter(const Context& c, int which);   // counters "ccd_queries" (0) / "ccd_skipped_pairs" (1) / "ccd_capped_pairs" (2)
 int64_t contact_sharded_searches(const Context& c);  // searches of a sharded problem whose sweep was dealt out to the ranks (contact.hip)
 void contact_shared_rows(Context& c, std::vector<int32_t>& rows);  // contact.hip
+// contact.hip: what the contact report reads of the detector — the collision meshes on the device, the sorted key list of the installed barrier tables and
+// their boundaries, the bound state arrays. Before the first search of a mesh set the meshes are not on the device yet: the view then does that search's
+// first step (prepare(), upload_meshes(): the mesh arrays are uploaded, the detector's position and box buffers allocated, its box cache marked stale).
+// Once a search has run, nothing the detector owns is written.
+struct ContactReportView
+{
+    const int32_t *cv_src, *cv_mesh, *tri, *tri_mesh, *edge, *edge_mesh, *mesh_kind;
+    const double *thick, *k, *X_rest, *rb_xloc;
+    const uint64_t* keys;            // sorted, n_keys of them (0 before the first search)
+    int64_t n_keys;
+    int bounds[22];                  // table t owns rows [bounds[t], bounds[t + 1])
+    int n_mesh, n_v, n_t, n_e;
+    int prim_bits;                   // bits of a primitive index inside a key (pack_key)
+    const std::vector<int32_t>*h_tri, *h_cv_src, *h_cv_mesh;
+};
+// sizes_only: the counts and host lists alone (n_keys, n_mesh, n_v, n_t, n_e, h_*); nothing is prepared, uploaded or allocated and the device pointers are null
+void contact_report_view(Context& c, ContactReportView& v, bool sizes_only);
+void contact_report_positions(Context& c, double* X_dev);  // k_contact_vertices at the current DoFs and the bound time step into X_dev [n_v][3]
+// contact_report.hip (records as contact_report.hpp lays them out); set 0: the accessors, 1: the host mirror's recording. Null outputs are skipped.
+void contact_report_sizes(Context& c, int64_t* n_rows, int64_t* n_vertices, int32_t* n_groups);  // what a report would hold; nothing is launched
+void contact_report_run(Context& c, int set);
+void contact_report_rows(Context& c, int set, int32_t* rows_i, double* rows_d, int64_t* n_rows);
+void contact_report_vertices(Context& c, int set, double* out, int32_t* group, int32_t* source_index, int64_t* n_vertices);
+void contact_report_pairs(Context& c, int set, double* out, int32_t* n_groups);
+int64_t contact_report_long_rows(Context& c);  // counter "contact_report_long_rows"
 int register_potential(Context& c, const char* name, const int32_t* conn, int32_t n_elem, int32_t conn_stride, const mistark_binding* bindings, int32_t n_bindings);
 void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_abs = nullptr, bool lazy = false);
 void reduce_dot_and_max_abs(Context& c, const double* a, const double* b, int64_t n, double* dot, double* max_abs_a);

@@ -28,6 +28,11 @@ int budget_record_inertia(mistark_ctx* ctx, int slot, int potential, const doubl
 int budget_record_rigid(mistark_ctx* ctx, int slot, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3]);
 // out[n] of slot `slot`
 int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n);
+// contact report (contact_report.hip) of the current state into the device set of the host mirror; its three parts (null outputs are skipped, the counts
+// always come back)
+int contact_report_record(mistark_ctx* ctx);
+int contact_report_fetch(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows, double* vert, int32_t* group, int32_t* source_index, int64_t* n_vertices, double* pairs,
+                         int32_t* n_groups);
 // registry name of every potential in id order, and whether it is user-defined
 int potential_names(mistark_ctx* ctx, std::vector<std::string>& names, std::vector<char>& custom);
 

@@ -118,6 +118,12 @@ void EnergyFrictionalContact::disable_collision(const Handler& a, const Handler&
     disabled_pairs.push_back({std::min(a.get_idx(), b.get_idx()), std::max(a.get_idx(), b.get_idx())});
     stark.mark_registration_dirty();
 }
+void EnergyFrictionalContact::set_label(const Handler& h, const std::string& label)
+{
+    if (h.get_idx() < 0) return;
+    if (group_labels.size() <= (size_t)h.get_idx()) group_labels.resize((size_t)h.get_idx() + 1);
+    group_labels[(size_t)h.get_idx()] = label;
+}
 void EnergyFrictionalContact::register_potentials(mistark_ctx* ctx)
 {
     id_k = -1;
@@ -138,6 +144,8 @@ void EnergyFrictionalContact::register_potentials(mistark_ctx* ctx)
     a.rb_t0 = rb->id_t0;
     a.rb_q0 = rb->id_q0_;
     stark.check(mistark_contact_init(ctx, &a));
+    group_labels.resize(contact_thicknesses.size());
+    stark.contact_labels = &group_labels;
     for (const Mesh& m : meshes) {
         stark.check(mistark_contact_add_mesh(ctx, m.kind, m.idx_in_ps, m.verts.data(), (int32_t)m.verts.size(), m.triangles.empty() ? nullptr : m.triangles[0].data(),
                                              (int32_t)m.triangles.size(), m.edges.empty() ? nullptr : m.edges[0].data(), (int32_t)m.edges.size()));

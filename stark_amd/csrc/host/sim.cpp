@@ -56,6 +56,8 @@ void Stark::ensure_registered()
     forces_recorded = false;  // (recorded vectors live in the context just replaced)
     stress_recorded = false;
     budget_recorded = false;
+    contacts_recorded = false;
+    contact_labels = nullptr;
     budget_inertia_sources.clear();
     budget_rigid_source = BudgetRigidSource{};
     for (auto* m : models) m->register_dofs(ctx);
@@ -219,6 +221,12 @@ bool Stark::run_one_step()
             budget_time = current_time + dt;
             budget_recorded = true;
         }
+        if (contact_recording && contact_labels) {
+            for (auto& f : n.before_energy_evaluation) f();  // (as force recording: the installed tables are then this state's)
+            check(contact_report_record(ctx));
+            contacts_time = current_time + dt;
+            contacts_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -339,6 +347,31 @@ void Stark::get_budget(BudgetReport& out)
     };
     for (const BudgetInertiaSource& src : budget_inertia_sources) fetch_records(src.n_groups, 0, src.labels);
     if (budget_rigid_source.n > 0) fetch_records(budget_rigid_source.n, 1, budget_rigid_source.labels);
+}
+void Stark::record_contacts(bool enabled)
+{
+    contact_recording = enabled;
+    contacts_recorded = false;
+}
+void Stark::get_contacts(ContactReport& out, bool sizes_only)
+{
+    if (!contact_recording) throw std::runtime_error("get_contacts: contact recording is off (record_contacts)");
+    out = ContactReport{};
+    if (ctx && !contact_labels) return;  // (no contact model: nothing to report)
+    if (!ctx || !contacts_recorded) throw std::runtime_error("get_contacts: no time step has been accepted since recording was switched on");
+    out.time = contacts_time;
+    check(contact_report_fetch(ctx, nullptr, nullptr, &out.n_rows, nullptr, nullptr, nullptr, &out.n_vertices, nullptr, &out.n_groups));
+    out.labels = *contact_labels;
+    out.labels.resize((size_t)out.n_groups);
+    if (sizes_only) return;
+    out.rows_i.resize(8 * (size_t)out.n_rows);
+    out.rows_d.resize(16 * (size_t)out.n_rows);
+    out.vertices.resize(5 * (size_t)out.n_vertices);
+    out.vertex_group.resize((size_t)out.n_vertices);
+    out.vertex_source.resize((size_t)out.n_vertices);
+    out.pairs.resize(8 * (size_t)out.n_groups * out.n_groups);
+    check(contact_report_fetch(ctx, out.rows_i.data(), out.rows_d.data(), &out.n_rows, out.vertices.data(), out.vertex_group.data(), out.vertex_source.data(), &out.n_vertices,
+                               out.pairs.data(), &out.n_groups));
 }
 std::string Stark::get_frame_path(const std::string& name) const
 {
@@ -1012,6 +1045,7 @@ Surface::Handler DeformablesPresets::add_surface(const std::string& label, const
     auto strain = tri->add(ps, T, p.strain);
     auto bending = deformables->discrete_shells->add(ps, T, p.bending);
     ContactHandler contact = interactions->contact->add_triangles(ps, T, p.contact);
+    interactions->contact->set_label(contact, label);
     if (!label.empty() && interactions->output) {
         interactions->output->add_triangle_mesh(label, ps, T);
         interactions->output->set_stress_source(1, p.strain.elasticity_only, pos, [tri]() { return tri->n_complete(); });
@@ -1041,6 +1075,7 @@ Volume::Handler DeformablesPresets::add_volume(const std::string& label, const s
     const bool with_output = !label.empty() && interactions->output;
     if (interactions->contact->is_active() || with_output) find_surface(surface, tri_to_tet_map, V, T);
     if (interactions->contact->is_active()) contact = interactions->contact->add_triangles(ps, surface, tri_to_tet_map, p.contact);
+    interactions->contact->set_label(contact, label);
     // the frame of a volume is its surface with the surface's own vertices (DeformablesPresets.cpp:74-76)
     if (with_output) {
         interactions->output->add_triangle_mesh(label, ps, surface, tri_to_tet_map);
@@ -1083,6 +1118,7 @@ RigidBody::Handler RigidBodyPresets::add(const std::string& label, double mass, 
     rigidbodies->inertia->labels[(size_t)body.get_idx()] = label;
     ContactHandler contact;
     if (interactions->contact->is_active()) contact = interactions->contact->add_triangles(body, V, T, cp);
+    interactions->contact->set_label(contact, label);
     if (!label.empty() && interactions->output) interactions->output->add_triangle_mesh(label, body, V, T);
     return {body, contact};
 }

@@ -183,6 +183,24 @@ public:
     };
     std::vector<BudgetInertiaSource> budget_inertia_sources;
     BudgetRigidSource budget_rigid_source;
+    // Contact recording (off by default; not in the reference): at the same place, after the before_energy_evaluation callbacks (the installed tables are
+    // then those of the end-of-step state), one contact report (include/mistark_contact.h "contact report": rows, vertex records, pair records) into a
+    // device set of its own; kept there until get_contacts() downloads it. Off: nothing is launched or allocated. A scene without contact records nothing
+    // and reports empty arrays.
+    struct ContactReport
+    {
+        std::vector<int32_t> rows_i;                      // [n_rows][8]
+        std::vector<double> rows_d, vertices, pairs;      // [n_rows][16], [n_vertices][5], [n_groups][n_groups][8]
+        std::vector<int32_t> vertex_group, vertex_source;  // [n_vertices]
+        std::vector<std::string> labels;                  // per group: the label of the preset that created it ("" otherwise)
+        int64_t n_rows = 0, n_vertices = 0;
+        int32_t n_groups = 0;
+        double time = 0.0;                                // simulation time of the accepted step
+    };
+    void record_contacts(bool enabled);
+    void get_contacts(ContactReport& out, bool sizes_only = false);  // sizes_only: counts, labels and time; nothing is downloaded
+    bool contact_recording = false, contacts_recorded = false;
+    const std::vector<std::string>* contact_labels = nullptr;  // noted by the contact model when it registers (null: the scene has no contact)
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -197,7 +215,7 @@ private:
     std::vector<std::string> force_groups;
     bool forces_recorded = false;  // ... in the current engine context
     Vec3 budget_about = {0.0, 0.0, 0.0};
-    double budget_time = 0.0;
+    double budget_time = 0.0, contacts_time = 0.0;
     std::vector<int32_t> budget_pots;       // the potentials of slot 0, as recorded
     std::vector<std::string> budget_names;  // ... and their names
     void _initialize();
@@ -674,6 +692,8 @@ public:
     void disable_collision(const Handler& a, const Handler& b);
     bool is_empty() const { return meshes.empty(); }
     bool is_active() const { return is_initialized; }
+    void set_label(const Handler& h, const std::string& label);  // the presets name their group (contact report)
+    std::vector<std::string> group_labels;                      // per group: "" unless a preset named it
     int64_t last_n_contacts = 0, last_n_friction_contacts = 0, n_detections = 0;
     void register_potentials(mistark_ctx* ctx) override;
     // off: no max_allowed_step callback at all (the line search is what it is without CCD); on: one callback

@@ -194,6 +194,38 @@ class Engine:
             out["bary"] = bary
         return out
 
+    # ---- contact report (include/mistark_contact.h "contact report") ------------------------------------------------------
+    def contact_report(self) -> dict:
+        """Rows of the installed barrier tables at the current DoFs, in table order: dict(ints [n, 8], doubles [n, 16], bounds [22] (table t owns rows
+        bounds[t]:bounds[t + 1]) and the named columns table, source, type, group_a, group_b, prim_a, prim_b, flags, d, dhat, point_a, point_b,
+        normal, mollifier, fn, E, params). No search runs; bit-reproducible."""
+        n = C.c_int64()
+        self._ck(self.L.mistark_contact_report(self.h, None, None, C.byref(n)))
+        ri = np.zeros((n.value, 8), dtype=np.int32)
+        rd = np.zeros((n.value, 16))
+        if n.value:
+            self._ck(self.L.mistark_contact_report(self.h, ri.ctypes.data, rd.ctypes.data, C.byref(n)))
+        return contact_rows_dict(ri, rd)
+
+    def contact_vertex_report(self) -> dict:
+        """Per collision vertex: dict(records [n, 5], gap, count, force, area, pressure, group, source_index)."""
+        n = C.c_int64()
+        self._ck(self.L.mistark_contact_vertex_report(self.h, None, None, None, C.byref(n)))
+        out = np.zeros((n.value, 5))
+        group, src = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._ck(self.L.mistark_contact_vertex_report(self.h, out.ctypes.data, group.ctypes.data, src.ctypes.data, C.byref(n)))
+        return contact_vertices_dict(out, group, src)
+
+    def contact_pair_report(self) -> np.ndarray:
+        """records [n_groups, n_groups, 8], entries ga <= gb filled: rows, smallest d, dhat, sum fn, sum fn n (on the lower group), sum E."""
+        g = C.c_int32()
+        self._ck(self.L.mistark_contact_pair_report(self.h, None, C.byref(g)))
+        out = np.zeros((g.value, g.value, 8))
+        if g.value:
+            self._ck(self.L.mistark_contact_pair_report(self.h, out.ctypes.data, C.byref(g)))
+        return out
+
     def contact_vertices(self) -> np.ndarray:
         n = C.c_int64()
         self._ck(self.L.mistark_contact_get_vertices(self.h, None, C.byref(n)))
@@ -424,3 +456,16 @@ class Engine:
         ms, n, b = C.c_double(), C.c_int64(), C.c_double()
         self._ck(self.L.mistark_spmv_timing(self.h, reset, C.byref(ms), C.byref(n), C.byref(b)))
         return ms.value, n.value, b.value
+
+
+def contact_rows_dict(ri, rd):
+    """The row arrays of a contact report with their columns named (views)."""
+    bounds = np.searchsorted(ri[:, 0], np.arange(22), side="left")
+    return dict(ints=ri, doubles=rd, bounds=bounds, table=ri[:, 0], source=ri[:, 1], type=ri[:, 2], group_a=ri[:, 3], group_b=ri[:, 4], prim_a=ri[:, 5], prim_b=ri[:, 6],
+                flags=ri[:, 7], d=rd[:, 0], dhat=rd[:, 1], point_a=rd[:, 2:5], point_b=rd[:, 5:8], normal=rd[:, 8:11], mollifier=rd[:, 11], fn=rd[:, 12], E=rd[:, 13],
+                params=rd[:, 14:16])
+
+
+def contact_vertices_dict(rec, group, source_index):
+    """The vertex records of a contact report with their columns named (views; count as integers)."""
+    return dict(records=rec, gap=rec[:, 0], count=rec[:, 1].astype(np.int64), force=rec[:, 2], area=rec[:, 3], pressure=rec[:, 4], group=group, source_index=source_index)

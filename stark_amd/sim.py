@@ -139,6 +139,8 @@ def _lib():
         L.mistark_sim_record_budget.argtypes = [p, C.c_int, D]
         I32 = C.POINTER(C.c_int32)
         L.mistark_sim_get_budget.argtypes = [p, I32, I32, I64, I64, D, p, p, p, p, p]
+        L.mistark_sim_record_contacts.argtypes = [p, C.c_int]
+        L.mistark_sim_get_contacts.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
         _bound = True
     return L
 
@@ -548,6 +550,27 @@ class Simulation:
                      angular_momentum=sum((o["angular_momentum"] for o in objects), np.zeros(3)), kinetic=sum(o["kinetic"] for o in objects),
                      gravitational=sum(o["gravitational"] for o in objects))
         return dict(potentials=potentials, objects=objects, total=total, time=t.value)
+
+    # ---- contact recording -------------------------------------------------------------------------------------------------
+    def record_contacts(self, on=True):
+        """Every accepted step then keeps the contact report of the state it converged at (rows of the installed barrier tables, vertex records,
+        group-pair records) on the device."""
+        self._ck(self.L.mistark_sim_record_contacts(self.h, int(bool(on))))
+
+    def contacts(self):
+        """The contact report of the last accepted step: dict(rows=Engine.contact_report()'s dict, vertices=Engine.contact_vertex_report()'s dict,
+        pairs [n_groups, n_groups, 8], labels [n_groups], time). Raises while recording is off."""
+        from .engine import contact_rows_dict, contact_vertices_dict
+        n, nv, lb, t, g = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double(), C.c_int32()
+        self._ck(self.L.mistark_sim_get_contacts(self.h, C.byref(n), C.byref(nv), C.byref(g), C.byref(lb), C.byref(t), None, None, None, None, None, None, None))
+        ri, rd = np.zeros((n.value, 8), dtype=np.int32), np.zeros((n.value, 16))
+        vert, vg, vs = np.zeros((nv.value, 5)), np.zeros(nv.value, dtype=np.int32), np.zeros(nv.value, dtype=np.int32)
+        pairs = np.zeros((g.value, g.value, 8))
+        labels = C.create_string_buffer(max(lb.value, 1))
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self._ck(self.L.mistark_sim_get_contacts(self.h, C.byref(n), C.byref(nv), C.byref(g), C.byref(lb), C.byref(t), ptr(ri), ptr(rd), ptr(vert), ptr(vg), ptr(vs), ptr(pairs),
+                                                 labels))
+        return dict(rows=contact_rows_dict(ri, rd), vertices=contact_vertices_dict(vert, vg, vs), pairs=pairs, labels=labels.value.decode().split("\n")[:-1], time=t.value)
 
     def engine_handle(self):
         return C.c_void_p(self.L.mistark_sim_engine(self.h))
