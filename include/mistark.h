@@ -418,7 +418,8 @@ int mistark_sync(mistark_ctx* ctx);
  * that were summed by a whole wavefront: more than 256 contributions), "stress_readouts" / "stress_long_rows" (the same two for the stress readout:
  * calls that launched, rows of the last nodal readout summed by a whole wavefront), "budget_readouts" / "budget_chunks" (budget readout calls that
  * launched, chunks of the element list the last inertia budget was summed in), "contact_reports" / "contact_report_long_rows" (contact report calls
- * that launched, mistark_contact.h; collision vertices of the last report summed by a whole wavefront). */
+ * that launched, mistark_contact.h; collision vertices of the last report summed by a whole wavefront), "friction_reports" / "friction_report_long_rows"
+ * (the same two for the friction report). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

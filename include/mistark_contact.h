@@ -123,6 +123,46 @@ int mistark_contact_vertex_report(mistark_ctx* ctx, double* out, int32_t* group,
  * the force on the lower-numbered group (ga == gb: in role order, on a from b) | 7 sum E. out nullable: n_groups alone. */
 int mistark_contact_pair_report(mistark_ctx* ctx, double* out, int32_t* n_groups);
 
+/* ---- friction report (opt-in, not in the reference) ------------------------------------------------------------------------
+ * What friction does at the current DoFs: which contacts stick and which slide, how fast, how much of mu fn is mobilised, which way the friction force
+ * points and how much power it takes out. A pipeline of its own beside mistark_eval, shaped like the contact report above: it reads the friction tables
+ * as the last mistark_contact_update_friction installed them (the lagged T, mu, fn and bary; nothing is classified or recomputed from positions), that
+ * search's key list (a copy the detector keeps for this report alone: a friction row does not carry its groups) and the velocities of the current DoFs
+ * (v1, rb_v1, rb_w1; rb_q0, rb_xloc, dt and epsv as bound), and writes only buffers of its own. No floating-point atomics; every sum runs in a fixed
+ * order over the row list and through a fixed tree, so two reports of one state give the same bits. It costs nothing unless it is called. Refused, with
+ * the cause in the message: sharded contexts, registration-only contexts, contexts without mistark_contact_init. Zero rows (vertex and pair records of
+ * zeros), not an error: before the first friction update, after a mesh was added and friction has not been updated since, with friction off or every mu
+ * zero (the friction search then routes no row).
+ *
+ * Everything is as the table's potential evaluates it. Roles follow the potential: v = v_B - v_A with B the side whose contact-point velocity the
+ * potential takes positive. That is the search's detected (A, B) — in friction_rb_d_ep / _tp the deformable point is A although the row lists it last —
+ * except in rows of friction_rb_d_pp and friction_rb_d_ee whose detected A is deformable: the reference lists and subtracts the rigid side there, so
+ * the rigid side is A. Contact-point velocity of a side: the bary combination of its vertices' velocities (a rigid vertex: rb_v1 + rb_w1 x (R1 xloc));
+ * u0 = T[0:3].v dt + 1.13e-9, u1 = T[3:6].v dt - 1.07e-9 (the reference's offsets), epsu = dt epsv; sticking iff |u| < epsu;
+ * E = 0.5 (mu fn / epsu) |u|^2 sticking, mu fn (|u| - epsu / 2) sliding; force on A: ft = c (u0 T[0:3] + u1 T[3:6]), c = mu fn / epsu sticking,
+ * mu fn / |u| sliding; on B: -ft. Torques on rigid bodies are not reported.
+ * Rows come in key order = table order: the rows of table t (21..34, friction_d_d_pp_C0 .. friction_rb_d_tp_C0) are contiguous and line up with
+ * mistark_contact_get_table's and mistark_contact_get_friction_data's.
+ *   rows_i [n][8]:  0 table | 1 row in that table | 2 kind (0 pp, 1 pe, 2 pt, 3 ee, 4 ep, 5 tp) | 3 group of A | 4 group of B | 5 rigid body of A or -1 |
+ *                   6 rigid body of B or -1 | 7 flags: +1 sliding, +2 mu fn == 0, +4 degenerate (a key outside the meshes — a detector bug, never seen —:
+ *                   a row of zeros that takes no part in the vertex and pair records)
+ *   rows_d [n][24]: 0 mu | 1 lagged fn | 2 epsu | 3 u0 | 4 u1 | 5 |u| | 6 slip speed |u| / dt | 7..9 v | 10..12 ft | 13 |ft| | 14 mobilised = |ft| / (mu fn),
+ *                   never above 1, 0 where mu fn == 0 | 15 dissipation = ft.v [W] | 16 E | 17 A-side parameter s (ee rows, else 0) | 18..20 B-side weights |
+ *                   21..23 zero. Node weights: A [1] or [1 - s, s]; B [1], [b0, b1], [b0, b1, b2] or [1 - t, t]; the force on a deformable node is +w ft
+ *                   on A and -w ft on B, the linear force on a rigid body +ft / -ft.
+ * Outputs are nullable; a call with every output NULL answers the size from host counts: nothing is launched, uploaded or allocated. Each call with an
+ * output runs the whole pipeline and downloads its own part; nothing is cached between calls (mistark_sim_record_friction runs it once per step). */
+int mistark_contact_friction_report(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows);
+/* out [n_collision_vertices][8]: 0 rows the vertex takes part in | 1 sliding ones among them | 2..4 friction force on the vertex = sum of s w ft over them
+ * (s = +1 on A, -1 on B, w the vertex's node weight) | 5 largest slip speed over them (0: none) | 6 area = a third of the current areas of the vertex's
+ * collision triangles (computed only while the report has rows, else 0) | 7 shear traction = |[2..4]| / [6] where [6] > 0, else 0. group, source_index as
+ * mistark_contact_vertex_report. */
+int mistark_contact_friction_vertex_report(mistark_ctx* ctx, double* out, int32_t* group, int32_t* source_index, int64_t* n_vertices);
+/* out [n_groups][n_groups][12], entries ga <= gb filled, the rest zero: 0 rows | 1 sliding rows | 2 sum fn | 3 sum mu fn | 4..6 sum ft oriented as the force
+ * on the lower-numbered group (ga == gb: in role order, on A) | 7 sum |ft| | 8 sum dissipation | 9 sum E | 10 largest slip speed | 11 [7] / [3] (0 where
+ * [3] is 0). out nullable: n_groups alone. */
+int mistark_contact_friction_pair_report(mistark_ctx* ctx, double* out, int32_t* n_groups);
+
 /* Binding recipe of one of the 35 potentials: (role, stride, connectivity column) per binding in the reference's order;
  * roles index the members of mistark_contact_arrays (0..11), 12 = T, 13 = mu, 14 = fn, 15 = bary. Returns n_bindings. */
 int mistark_contact_recipe(const char* potential, int32_t* conn_stride, int32_t* roles, int32_t* strides, int32_t* conn_cols);

@@ -252,6 +252,15 @@ int mistark_sim_record_contacts(mistark_sim* sim, int enabled);
  * An error while recording is off. */
 int mistark_sim_get_contacts(mistark_sim* sim, int64_t* n_rows, int64_t* n_vertices, int32_t* n_groups, int64_t* labels_bytes, double* time, int32_t* rows_i, double* rows_d,
                              double* vertices, int32_t* vertex_group, int32_t* vertex_source, double* pairs, char* labels);
+/* Friction recording (off by default; not in the reference), at the same place inside the step: one friction report (mistark_contact.h "friction report")
+ * of the friction tables installed at the start of the step, at the velocities the step converged to: rows, vertex records, group-pair records. Results
+ * stay on the device until they are asked for. With recording off nothing is launched or allocated. */
+int mistark_sim_record_friction(mistark_sim* sim, int enabled);
+/* The friction report of the last accepted step. Every output is nullable; a first call with the buffers NULL gives the sizes. rows_i [n_rows x 8],
+ * rows_d [n_rows x 24], vertices [n_vertices x 8], vertex_group / vertex_source [n_vertices], pairs [n_groups x n_groups x 12]; labels and time as
+ * mistark_sim_get_contacts. A scene without contact reports empty arrays. An error while recording is off. */
+int mistark_sim_get_friction(mistark_sim* sim, int64_t* n_rows, int64_t* n_vertices, int32_t* n_groups, int64_t* labels_bytes, double* time, int32_t* rows_i, double* rows_d,
+                             double* vertices, int32_t* vertex_group, int32_t* vertex_source, double* pairs, char* labels);
 /* The part of a time step before the Newton solve (Stark.cpp:145-156: before_time_step callbacks = friction tables at the start-of-step
  * geometry, rigid-body caches, v1 = 0) and the Newton callback that precedes every evaluation (contact tables at the current DoFs), as
  * separate calls: what the reference's harness does to take a stage snapshot at a given state (callbacks->run_before_time_step();

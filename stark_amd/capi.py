@@ -143,6 +143,9 @@ def lib():
     L.mistark_contact_report.argtypes = [p, p, p, C.POINTER(i64)]
     L.mistark_contact_vertex_report.argtypes = [p, p, p, p, C.POINTER(i64)]
     L.mistark_contact_pair_report.argtypes = [p, p, C.POINTER(C.c_int32)]
+    L.mistark_contact_friction_report.argtypes = [p, p, p, C.POINTER(i64)]
+    L.mistark_contact_friction_vertex_report.argtypes = [p, p, p, p, C.POINTER(i64)]
+    L.mistark_contact_friction_pair_report.argtypes = [p, p, C.POINTER(C.c_int32)]
     L.mistark_contact_recipe.argtypes = [C.c_char_p, C.POINTER(C.c_int32), p, p, p]
     L.mistark_cd_create.argtypes = [C.POINTER(p), C.c_int]
     L.mistark_cd_destroy.argtypes = [p]

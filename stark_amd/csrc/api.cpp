@@ -584,6 +584,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "budget_chunks") *out = c.n_budget_chunks;
     else if (n == "contact_reports") *out = c.n_contact_reports;
     else if (n == "contact_report_long_rows") *out = contact_report_long_rows(c);
+    else if (n == "friction_reports") *out = c.n_friction_reports;
+    else if (n == "friction_report_long_rows") *out = friction_report_long_rows(c);
     else if (n == "llt_path") *out = c.llt_last_path;
     else if (n == "llt_panel_rows") *out = c.llt_last_panel_rows;
     else if (n == "llt_panels") *out = c.llt_last_panels;
@@ -790,6 +792,41 @@ int mistark_contact_pair_report(mistark_ctx* ctx, double* out, int32_t* n_groups
     }
     contact_report_run(ctx->c, 0);
     contact_report_pairs(ctx->c, 0, out, n_groups);
+    API_END(0)
+}
+
+// ---- friction report (friction_report.hip) -------------------------------------------------------------------------------
+int mistark_contact_friction_report(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows)
+{
+    API_BEGIN
+    if (!rows_i && !rows_d) {  // the size query launches nothing
+        friction_report_sizes(ctx->c, n_rows, nullptr, nullptr);
+        return 0;
+    }
+    friction_report_run(ctx->c, 0);
+    friction_report_rows(ctx->c, 0, rows_i, rows_d, n_rows);
+    API_END(0)
+}
+int mistark_contact_friction_vertex_report(mistark_ctx* ctx, double* out, int32_t* group, int32_t* source_index, int64_t* n_vertices)
+{
+    API_BEGIN
+    if (!out && !group && !source_index) {
+        friction_report_sizes(ctx->c, nullptr, n_vertices, nullptr);
+        return 0;
+    }
+    friction_report_run(ctx->c, 0);
+    friction_report_vertices(ctx->c, 0, out, group, source_index, n_vertices);
+    API_END(0)
+}
+int mistark_contact_friction_pair_report(mistark_ctx* ctx, double* out, int32_t* n_groups)
+{
+    API_BEGIN
+    if (!out) {
+        friction_report_sizes(ctx->c, nullptr, nullptr, n_groups);
+        return 0;
+    }
+    friction_report_run(ctx->c, 0);
+    friction_report_pairs(ctx->c, 0, out, n_groups);
     API_END(0)
 }
 
@@ -1516,6 +1553,21 @@ int contact_report_fetch(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int6
     contact_report_rows(ctx->c, 1, rows_i, rows_d, n_rows);
     contact_report_vertices(ctx->c, 1, vert, group, source_index, n_vertices);
     contact_report_pairs(ctx->c, 1, pairs, n_groups);
+    API_END(0)
+}
+int friction_report_record(mistark_ctx* ctx)
+{
+    API_BEGIN
+    friction_report_run(ctx->c, 1);
+    API_END(0)
+}
+int friction_report_fetch(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows, double* vert, int32_t* group, int32_t* source_index, int64_t* n_vertices, double* pairs,
+                          int32_t* n_groups)
+{
+    API_BEGIN
+    friction_report_rows(ctx->c, 1, rows_i, rows_d, n_rows);
+    friction_report_vertices(ctx->c, 1, vert, group, source_index, n_vertices);
+    friction_report_pairs(ctx->c, 1, pairs, n_groups);
     API_END(0)
 }
 int potential_names(mistark_ctx* ctx, std::vector<std::string>& names, std::vector<char>& custom)

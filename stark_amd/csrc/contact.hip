@@ -1243,6 +1243,11 @@ struct ContactSystem : BoxSweep
     DevBuf<uint64_t> keys, keys_alt, prev;
     bool brute_force = false;  // ablation / fallback: LDS-tiled all-pairs kernels
     int64_t n_prev = -1;  // keys of the barrier tables currently installed (-1: none)
+    // sorted keys of the friction tables as the last friction search routed them (row order = key order): keys / keys_alt are overwritten by the next
+    // barrier search, and a friction row does not carry its groups. Read by the friction report alone (friction_report.hip). 0 after a change of
+    // the mesh set, until the next friction search.
+    DevBuf<uint64_t> fr_keys;
+    int64_t n_fr = 0;
     DevBuf<int> counters;  // [0] candidates, [1] intersections, [2] differs, [8..8+N_TABLES] bounds, [48..51] box list (k_bp_fill; [51] = entries needed)
     // result of the last barrier-table search and the inputs it saw (Context::data_version, dt): an identical request is answered from here
     int n_last = 0;  // keys found by the last search (sizes the padded sort of the next one)
@@ -1408,6 +1413,7 @@ int contact_add_mesh(Context& c, int kind, int idx_in_ps, const int32_t* vidx, i
     if (kind == MISTARK_CONTACT_RIGIDBODY) cs.disabled_pairs.push_back({g, g});
     cs.meshes_dirty = true;
     cs.n_prev = -1;
+    cs.n_fr = 0;
     return g;
 }
 template <class T>
@@ -1838,6 +1844,10 @@ int64_t detect_and_route(Context& c, double dt, bool friction)
         cs.cache_n = n;
         cs.searched_version = c.data_version;
         cs.searched_dt = dt;
+    } else {
+        cs.fr_keys.ensure(std::max<size_t>((size_t)n, 1));
+        if (n > 0) copy_async(c.stream, cs.fr_keys.p, sorted, (size_t)n * sizeof(uint64_t));
+        cs.n_fr = n;
     }
     lap(6);
     return n;
@@ -1886,6 +1896,45 @@ void contact_report_positions(Context& c, double* X_dev)
     hipLaunchKernelGGL(k_contact_vertices, dim3((cs.n_v + CB - 1) / CB), dim3(CB), 0, c.stream, d, arr_dev(c, cs.arr.x0), arr_dev(c, cs.arr.v1), arr_dev(c, cs.arr.rb_xloc),
                        arr_dev(c, cs.arr.rb_v1), arr_dev(c, cs.arr.rb_w1), arr_dev(c, cs.arr.rb_t0), arr_dev(c, cs.arr.rb_q0), a.host[0], X_dev);
     MS_CHECK(hipGetLastError());
+}
+// ---- friction report (friction_report.hip): read access to the friction tables as the last friction search installed them -------------------
+void friction_report_view(Context& c, FrictionReportView& v, bool sizes_only)
+{
+    ContactSystem& cs = CS(c);
+    v = FrictionReportView{};
+    v.n_mesh = (int)cs.meshes.size(); v.n_v = cs.n_v; v.n_t = cs.n_t; v.n_e = cs.n_e;
+    v.h_tri = &cs.h_tri; v.h_cv_src = &cs.h_cv_src; v.h_cv_mesh = &cs.h_cv_mesh;
+    v.n_keys = cs.meshes.empty() ? 0 : cs.n_fr;
+    if (sizes_only || v.n_keys == 0) return;
+    prepare(c);
+    // (a friction search has run on this mesh set: the meshes are on the device. They are left alone even when marked stale, as the contact report does)
+    v.cv_src = cs.cv_src.p; v.cv_mesh = cs.cv_mesh.p; v.tri = cs.tri.p; v.tri_mesh = cs.tri_mesh.p; v.edge = cs.edge.p; v.edge_mesh = cs.edge_mesh.p;
+    v.mesh_kind = cs.mesh_kind.p; v.mesh_idx = cs.mesh_idx.p;
+    v.v1 = arr_dev(c, cs.arr.v1); v.rb_v1 = arr_dev(c, cs.arr.rb_v1); v.rb_w1 = arr_dev(c, cs.arr.rb_w1); v.rb_q0 = arr_dev(c, cs.arr.rb_q0); v.rb_xloc = arr_dev(c, cs.arr.rb_xloc);
+    v.prim_bits = PRIM_BITS;
+    v.keys = cs.fr_keys.p;
+    const Array& adt = c.arrays[cs.arr.dt];
+    const Array& aeps = c.arrays[cs.arr.epsv];
+    if (!adt.host || adt.n_items < 1 || !aeps.host || aeps.n_items < 1) throw Error("friction report: the dt and epsv arrays have no host value");
+    v.dt = adt.host[0];
+    v.epsv = aeps.host[0];
+    int at = 0;
+    for (int t = N_CONTACT_TABLES; t < N_TABLES; t++) {
+        const ContactSystem::Table& T = cs.tables[t];
+        FrictionReportView::Table& o = v.tables[t - N_CONTACT_TABLES];
+        o.start = at;
+        if (T.pot < 0) continue;
+        o.n = T.n;
+        o.stride = T.stride;
+        o.nbary = T.nbary;
+        o.conn = T.conn.p;
+        o.T = c.arrays[T.a_T].dev;
+        o.mu = c.arrays[T.a_mu].dev;
+        o.fn = c.arrays[T.a_fn].dev;
+        o.bary = T.a_bary >= 0 ? c.arrays[T.a_bary].dev : nullptr;
+        at += T.n;
+    }
+    if (at != (int)v.n_keys) throw Error("friction report: the installed tables hold " + std::to_string(at) + " rows, the key list " + std::to_string(v.n_keys));
 }
 namespace {
 int64_t count_intersections_uncached(Context& c, double dt);

@@ -604,6 +604,30 @@ struct Context
     bool cr_stat_valid = false;
     int64_t n_contact_reports = 0;   // counter "contact_reports": calls that launched
 
+    // Friction report (friction_report.hip): the fifth pipeline beside eval(). Rows of the friction tables as the last friction search installed them
+    // (lagged T, mu, fn, bary; the search's own key list) at the velocities of the current DoFs, up to five signed (collision vertex, weight)
+    // contributions per row sorted by collision vertex and summed in sorted order -> per-vertex records, rows sorted by group pair (stable) and summed
+    // by one workgroup per pair -> per-pair records. Nothing but these buffers is written.
+    struct FrictionReportSet         // [0]: what the accessors return, [1]: what the host mirror records inside a time step and keeps on the device
+    {
+        DevBuf<int32_t> rows_i;      // [n_rows][8]
+        DevBuf<double> rows_d;       // [n_rows][24]
+        DevBuf<double> vert;         // [n_v][8]
+        DevBuf<double> pair;         // [n_groups][n_groups][12]
+        int64_t n_rows = -1;         // -1: nothing yet
+        int64_t n_v = 0;
+        int n_groups = 0;
+    };
+    FrictionReportSet frr_set[2];
+    DevBuf<double> frr_X, frr_w;     // collision vertex positions of the report's own [n_v][3] (areas); signed weight of every contribution [5 n_rows]
+    DevBuf<uint32_t> frr_key, frr_key_alt, frr_val, frr_val_alt;
+    DevBuf<uint8_t> frr_cub_tmp, frr_tables;  // frr_tables: the report's own table views [14]
+    DevBuf<int32_t> frr_inc;         // triangle incidence of the collision vertices (as cr_inc), built once per mesh set
+    int frr_inc_meshes = -1;
+    DevBuf<uint32_t> frr_stat;       // [0]: vertices of the last report summed by a whole wavefront (counter "friction_report_long_rows")
+    bool frr_stat_valid = false;
+    int64_t n_friction_reports = 0;  // counter "friction_reports": calls that launched
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -688,6 +712,34 @@ void contact_report_rows(Context& c, int set, int32_t* rows_i, double* rows_d, i
 void contact_report_vertices(Context& c, int set, double* out, int32_t* group, int32_t* source_index, int64_t* n_vertices);
 void contact_report_pairs(Context& c, int set, double* out, int32_t* n_groups);
 int64_t contact_report_long_rows(Context& c);  // counter "contact_report_long_rows"
+// contact.hip: what the friction report reads — the collision meshes on the device, the sorted key list the last friction search routed (row order = key
+// order), the 14 friction tables as installed (host counts, device pointers of conn / T / mu / fn / bary), the bound velocity arrays, dt and epsv. Nothing
+// is written; with no friction rows (no friction search yet, mesh set changed since, friction off) n_keys is 0 and the device pointers are null.
+struct FrictionReportView
+{
+    struct Table
+    {
+        const int32_t* conn = nullptr;
+        const double *T = nullptr, *mu = nullptr, *fn = nullptr, *bary = nullptr;
+        int stride = 0, nbary = 0, start = 0, n = 0;
+    };
+    const int32_t *cv_src, *cv_mesh, *tri, *tri_mesh, *edge, *edge_mesh, *mesh_kind, *mesh_idx;
+    const double *v1, *rb_v1, *rb_w1, *rb_q0, *rb_xloc;
+    const uint64_t* keys;
+    int64_t n_keys;
+    Table tables[14];                // tables 21..34
+    double dt, epsv;
+    int n_mesh, n_v, n_t, n_e, prim_bits;
+    const std::vector<int32_t>*h_tri, *h_cv_src, *h_cv_mesh;
+};
+void friction_report_view(Context& c, FrictionReportView& v, bool sizes_only);
+// friction_report.hip (records as friction_report.hpp lays them out); set 0: the accessors, 1: the host mirror's recording. Null outputs are skipped.
+void friction_report_sizes(Context& c, int64_t* n_rows, int64_t* n_vertices, int32_t* n_groups);  // what a report would hold; nothing is launched
+void friction_report_run(Context& c, int set);
+void friction_report_rows(Context& c, int set, int32_t* rows_i, double* rows_d, int64_t* n_rows);
+void friction_report_vertices(Context& c, int set, double* out, int32_t* group, int32_t* source_index, int64_t* n_vertices);
+void friction_report_pairs(Context& c, int set, double* out, int32_t* n_groups);
+int64_t friction_report_long_rows(Context& c);  // counter "friction_report_long_rows"
 int register_potential(Context& c, const char* name, const int32_t* conn, int32_t n_elem, int32_t conn_stride, const mistark_binding* bindings, int32_t n_bindings);
 void eval(Context& c, int mode, double* E, double* grad_host, double* grad_max_abs = nullptr, bool lazy = false);
 void reduce_dot_and_max_abs(Context& c, const double* a, const double* b, int64_t n, double* dot, double* max_abs_a);

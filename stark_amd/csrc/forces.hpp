@@ -33,6 +33,10 @@ int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n);
 int contact_report_record(mistark_ctx* ctx);
 int contact_report_fetch(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows, double* vert, int32_t* group, int32_t* source_index, int64_t* n_vertices, double* pairs,
                          int32_t* n_groups);
+// friction report (friction_report.hip), likewise
+int friction_report_record(mistark_ctx* ctx);
+int friction_report_fetch(mistark_ctx* ctx, int32_t* rows_i, double* rows_d, int64_t* n_rows, double* vert, int32_t* group, int32_t* source_index, int64_t* n_vertices, double* pairs,
+                          int32_t* n_groups);
 // registry name of every potential in id order, and whether it is user-defined
 int potential_names(mistark_ctx* ctx, std::vector<std::string>& names, std::vector<char>& custom);
 

@@ -57,6 +57,7 @@ void Stark::ensure_registered()
     stress_recorded = false;
     budget_recorded = false;
     contacts_recorded = false;
+    friction_recorded = false;
     contact_labels = nullptr;
     budget_inertia_sources.clear();
     budget_rigid_source = BudgetRigidSource{};
@@ -227,6 +228,11 @@ bool Stark::run_one_step()
             contacts_time = current_time + dt;
             contacts_recorded = true;
         }
+        if (friction_recording && contact_labels) {  // (the friction tables are those of the start of the step: no callback runs)
+            check(friction_report_record(ctx));
+            friction_time = current_time + dt;
+            friction_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -372,6 +378,31 @@ void Stark::get_contacts(ContactReport& out, bool sizes_only)
     out.pairs.resize(8 * (size_t)out.n_groups * out.n_groups);
     check(contact_report_fetch(ctx, out.rows_i.data(), out.rows_d.data(), &out.n_rows, out.vertices.data(), out.vertex_group.data(), out.vertex_source.data(), &out.n_vertices,
                                out.pairs.data(), &out.n_groups));
+}
+void Stark::record_friction(bool enabled)
+{
+    friction_recording = enabled;
+    friction_recorded = false;
+}
+void Stark::get_friction(FrictionReport& out, bool sizes_only)
+{
+    if (!friction_recording) throw std::runtime_error("get_friction: friction recording is off (record_friction)");
+    out = FrictionReport{};
+    if (ctx && !contact_labels) return;  // (no contact model: nothing to report)
+    if (!ctx || !friction_recorded) throw std::runtime_error("get_friction: no time step has been accepted since recording was switched on");
+    out.time = friction_time;
+    check(friction_report_fetch(ctx, nullptr, nullptr, &out.n_rows, nullptr, nullptr, nullptr, &out.n_vertices, nullptr, &out.n_groups));
+    out.labels = *contact_labels;
+    out.labels.resize((size_t)out.n_groups);
+    if (sizes_only) return;
+    out.rows_i.resize(8 * (size_t)out.n_rows);
+    out.rows_d.resize(24 * (size_t)out.n_rows);
+    out.vertices.resize(8 * (size_t)out.n_vertices);
+    out.vertex_group.resize((size_t)out.n_vertices);
+    out.vertex_source.resize((size_t)out.n_vertices);
+    out.pairs.resize(12 * (size_t)out.n_groups * out.n_groups);
+    check(friction_report_fetch(ctx, out.rows_i.data(), out.rows_d.data(), &out.n_rows, out.vertices.data(), out.vertex_group.data(), out.vertex_source.data(), &out.n_vertices,
+                                out.pairs.data(), &out.n_groups));
 }
 std::string Stark::get_frame_path(const std::string& name) const
 {

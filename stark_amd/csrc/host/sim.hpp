@@ -201,6 +201,22 @@ public:
     void get_contacts(ContactReport& out, bool sizes_only = false);  // sizes_only: counts, labels and time; nothing is downloaded
     bool contact_recording = false, contacts_recorded = false;
     const std::vector<std::string>* contact_labels = nullptr;  // noted by the contact model when it registers (null: the scene has no contact)
+    // Friction recording (off by default; not in the reference): at the same place one friction report (include/mistark_contact.h "friction report": rows
+    // of the friction tables installed at the start of the step, at the converged velocities; vertex records; pair records) into a device set of its
+    // own, kept there until get_friction() downloads it. Off: nothing is launched or allocated. A scene without contact records nothing.
+    struct FrictionReport
+    {
+        std::vector<int32_t> rows_i;                      // [n_rows][8]
+        std::vector<double> rows_d, vertices, pairs;      // [n_rows][24], [n_vertices][8], [n_groups][n_groups][12]
+        std::vector<int32_t> vertex_group, vertex_source;  // [n_vertices]
+        std::vector<std::string> labels;                  // per group: the label of the preset that created it ("" otherwise)
+        int64_t n_rows = 0, n_vertices = 0;
+        int32_t n_groups = 0;
+        double time = 0.0;                                // simulation time of the accepted step
+    };
+    void record_friction(bool enabled);
+    void get_friction(FrictionReport& out, bool sizes_only = false);  // sizes_only: counts, labels and time; nothing is downloaded
+    bool friction_recording = false, friction_recorded = false;
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -215,7 +231,7 @@ private:
     std::vector<std::string> force_groups;
     bool forces_recorded = false;  // ... in the current engine context
     Vec3 budget_about = {0.0, 0.0, 0.0};
-    double budget_time = 0.0, contacts_time = 0.0;
+    double budget_time = 0.0, contacts_time = 0.0, friction_time = 0.0;
     std::vector<int32_t> budget_pots;       // the potentials of slot 0, as recorded
     std::vector<std::string> budget_names;  // ... and their names
     void _initialize();

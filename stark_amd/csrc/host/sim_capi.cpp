@@ -825,6 +825,34 @@ int mistark_sim_get_contacts(mistark_sim* s, int64_t* n_rows, int64_t* n_vertice
     if (labels) std::memcpy(labels, lb.c_str(), lb.size() + 1);
     SIM_END
 }
+int mistark_sim_record_friction(mistark_sim* s, int enabled)
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_friction(enabled != 0);
+    SIM_END
+}
+int mistark_sim_get_friction(mistark_sim* s, int64_t* n_rows, int64_t* n_vertices, int32_t* n_groups, int64_t* labels_bytes, double* time, int32_t* rows_i, double* rows_d,
+                             double* vertices, int32_t* vertex_group, int32_t* vertex_source, double* pairs, char* labels)
+{
+    SIM_BEGIN
+    Stark::FrictionReport r;
+    s->sim->get_stark().get_friction(r, !rows_i && !rows_d && !vertices && !vertex_group && !vertex_source && !pairs);  // (the size query downloads nothing)
+    std::string lb;
+    for (const auto& l : r.labels) lb += l + "\n";
+    if (n_rows) *n_rows = r.n_rows;
+    if (n_vertices) *n_vertices = r.n_vertices;
+    if (n_groups) *n_groups = r.n_groups;
+    if (labels_bytes) *labels_bytes = (int64_t)lb.size() + 1;
+    if (time) *time = r.time;
+    if (rows_i) std::copy(r.rows_i.begin(), r.rows_i.end(), rows_i);
+    if (rows_d) std::copy(r.rows_d.begin(), r.rows_d.end(), rows_d);
+    if (vertices) std::copy(r.vertices.begin(), r.vertices.end(), vertices);
+    if (vertex_group) std::copy(r.vertex_group.begin(), r.vertex_group.end(), vertex_group);
+    if (vertex_source) std::copy(r.vertex_source.begin(), r.vertex_source.end(), vertex_source);
+    if (pairs) std::copy(r.pairs.begin(), r.pairs.end(), pairs);
+    if (labels) std::memcpy(labels, lb.c_str(), lb.size() + 1);
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

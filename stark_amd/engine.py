@@ -226,6 +226,39 @@ class Engine:
             self._ck(self.L.mistark_contact_pair_report(self.h, out.ctypes.data, C.byref(g)))
         return out
 
+    # ---- friction report (include/mistark_contact.h "friction report") ----------------------------------------------------
+    def friction_report(self) -> dict:
+        """Rows of the installed friction tables at the velocities of the current DoFs, in table order: dict(ints [n, 8], doubles [n, 24], bounds [15]
+        (table 21 + t owns rows bounds[t]:bounds[t + 1]) and the named columns table, row, kind, group_a, group_b, body_a, body_b, flags, mu, fn, epsu,
+        u, slip, slip_speed, v, ft, ft_norm, mobilised, dissipation, E, param_a, weights_b). No search runs; bit-reproducible."""
+        n = C.c_int64()
+        self._ck(self.L.mistark_contact_friction_report(self.h, None, None, C.byref(n)))
+        ri = np.zeros((n.value, 8), dtype=np.int32)
+        rd = np.zeros((n.value, 24))
+        if n.value:
+            self._ck(self.L.mistark_contact_friction_report(self.h, ri.ctypes.data, rd.ctypes.data, C.byref(n)))
+        return friction_rows_dict(ri, rd)
+
+    def friction_vertex_report(self) -> dict:
+        """Per collision vertex: dict(records [n, 8], count, sliding, force [n, 3], slip_speed, area, traction, group, source_index)."""
+        n = C.c_int64()
+        self._ck(self.L.mistark_contact_friction_vertex_report(self.h, None, None, None, C.byref(n)))
+        out = np.zeros((n.value, 8))
+        group, src = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._ck(self.L.mistark_contact_friction_vertex_report(self.h, out.ctypes.data, group.ctypes.data, src.ctypes.data, C.byref(n)))
+        return friction_vertices_dict(out, group, src)
+
+    def friction_pair_report(self) -> np.ndarray:
+        """records [n_groups, n_groups, 12], entries ga <= gb filled: rows, sliding rows, sum fn, sum mu fn, sum ft (on the lower group), sum |ft|, sum
+        dissipation, sum E, largest slip speed, sum |ft| / sum mu fn."""
+        g = C.c_int32()
+        self._ck(self.L.mistark_contact_friction_pair_report(self.h, None, C.byref(g)))
+        out = np.zeros((g.value, g.value, 12))
+        if g.value:
+            self._ck(self.L.mistark_contact_friction_pair_report(self.h, out.ctypes.data, C.byref(g)))
+        return out
+
     def contact_vertices(self) -> np.ndarray:
         n = C.c_int64()
         self._ck(self.L.mistark_contact_get_vertices(self.h, None, C.byref(n)))
@@ -469,3 +502,17 @@ def contact_rows_dict(ri, rd):
 def contact_vertices_dict(rec, group, source_index):
     """The vertex records of a contact report with their columns named (views; count as integers)."""
     return dict(records=rec, gap=rec[:, 0], count=rec[:, 1].astype(np.int64), force=rec[:, 2], area=rec[:, 3], pressure=rec[:, 4], group=group, source_index=source_index)
+
+
+def friction_rows_dict(ri, rd):
+    """The row arrays of a friction report with their columns named (views)."""
+    bounds = np.searchsorted(ri[:, 0], 21 + np.arange(15), side="left")
+    return dict(ints=ri, doubles=rd, bounds=bounds, table=ri[:, 0], row=ri[:, 1], kind=ri[:, 2], group_a=ri[:, 3], group_b=ri[:, 4], body_a=ri[:, 5], body_b=ri[:, 6],
+                flags=ri[:, 7], mu=rd[:, 0], fn=rd[:, 1], epsu=rd[:, 2], u=rd[:, 3:5], slip=rd[:, 5], slip_speed=rd[:, 6], v=rd[:, 7:10], ft=rd[:, 10:13], ft_norm=rd[:, 13],
+                mobilised=rd[:, 14], dissipation=rd[:, 15], E=rd[:, 16], param_a=rd[:, 17], weights_b=rd[:, 18:21])
+
+
+def friction_vertices_dict(rec, group, source_index):
+    """The vertex records of a friction report with their columns named (views; counts as integers)."""
+    return dict(records=rec, count=rec[:, 0].astype(np.int64), sliding=rec[:, 1].astype(np.int64), force=rec[:, 2:5], slip_speed=rec[:, 5], area=rec[:, 6],
+                traction=rec[:, 7], group=group, source_index=source_index)

@@ -141,6 +141,8 @@ def _lib():
         L.mistark_sim_get_budget.argtypes = [p, I32, I32, I64, I64, D, p, p, p, p, p]
         L.mistark_sim_record_contacts.argtypes = [p, C.c_int]
         L.mistark_sim_get_contacts.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
+        L.mistark_sim_record_friction.argtypes = [p, C.c_int]
+        L.mistark_sim_get_friction.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
         _bound = True
     return L
 
@@ -571,6 +573,27 @@ class Simulation:
         self._ck(self.L.mistark_sim_get_contacts(self.h, C.byref(n), C.byref(nv), C.byref(g), C.byref(lb), C.byref(t), ptr(ri), ptr(rd), ptr(vert), ptr(vg), ptr(vs), ptr(pairs),
                                                  labels))
         return dict(rows=contact_rows_dict(ri, rd), vertices=contact_vertices_dict(vert, vg, vs), pairs=pairs, labels=labels.value.decode().split("\n")[:-1], time=t.value)
+
+    # ---- friction recording ------------------------------------------------------------------------------------------------
+    def record_friction(self, on=True):
+        """Every accepted step then keeps the friction report of the state it converged at (rows of the friction tables installed at the start of the step,
+        vertex records, group-pair records) on the device."""
+        self._ck(self.L.mistark_sim_record_friction(self.h, int(bool(on))))
+
+    def friction(self):
+        """The friction report of the last accepted step: dict(rows=Engine.friction_report()'s dict, vertices=Engine.friction_vertex_report()'s dict,
+        pairs [n_groups, n_groups, 12], labels [n_groups], time). Raises while recording is off."""
+        from .engine import friction_rows_dict, friction_vertices_dict
+        n, nv, lb, t, g = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double(), C.c_int32()
+        self._ck(self.L.mistark_sim_get_friction(self.h, C.byref(n), C.byref(nv), C.byref(g), C.byref(lb), C.byref(t), None, None, None, None, None, None, None))
+        ri, rd = np.zeros((n.value, 8), dtype=np.int32), np.zeros((n.value, 24))
+        vert, vg, vs = np.zeros((nv.value, 8)), np.zeros(nv.value, dtype=np.int32), np.zeros(nv.value, dtype=np.int32)
+        pairs = np.zeros((g.value, g.value, 12))
+        labels = C.create_string_buffer(max(lb.value, 1))
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self._ck(self.L.mistark_sim_get_friction(self.h, C.byref(n), C.byref(nv), C.byref(g), C.byref(lb), C.byref(t), ptr(ri), ptr(rd), ptr(vert), ptr(vg), ptr(vs), ptr(pairs),
+                                                 labels))
+        return dict(rows=friction_rows_dict(ri, rd), vertices=friction_vertices_dict(vert, vg, vs), pairs=pairs, labels=labels.value.decode().split("\n")[:-1], time=t.value)
 
     def engine_handle(self):
         return C.c_void_p(self.L.mistark_sim_engine(self.h))
