@@ -186,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void k_project_eig(double* __restrict__ elem
     for (int t = lane; t < nn; t += 64) {
         const int i = t / n, j = t - i * n;
         double acc = 0.0;
-        for (int k = 0; k < n; k++) acc += V[i * n + k] * sL[wave][k] * V[j * n + k];
+        for (int k = 0; k < n; k++) acc = fma(V[i * n + k] * V[j * n + k], sL[wave][k], acc);  // (V_ik V_jk) l_k: symmetric in (i, j) to the bit, as project_cols_body
         const int ba = i / 3, ii = i - 3 * ba, bb = j / 3, jj = j - 3 * bb;
         const size_t blk = (size_t)(ba * NB + bb) * n_elem + e;
         double* dst = elemH + (size_t)(ba * NB + bb) * hs + (size_t)pe * 9 + ii * 3 + jj;
