@@ -410,7 +410,8 @@ int mistark_sync(mistark_ctx* ctx);
  * "contact_searches" / "contact_repeated_searches" (barrier-table searches that ran on the device / that ran at the state the previous one had
  * searched: 0 unless the option no_contact_cache is set), "eval_pgh_issue_us" / "eval_pgh_wait_us" (host microseconds of the P+g+H evaluations:
  * issuing their launches / waiting for their read-backs), "ccd_queries" / "ccd_skipped_pairs" / "ccd_capped_pairs" (mistark_contact_max_step: queries,
- * candidate pairs skipped because they touch at the line search's start, pairs whose additive CCD stopped at its iteration cap),
+ * candidate pairs skipped because they touch at the line search's start, pairs whose additive CCD stopped at its iteration cap), "ccd_rounds" /
+ * "ccd_pad_bound_pairs" (mistark_contact_max_step_ex: passes of the CCD chain its queries made, pairs still pad-bound when a query's rounds ran out),
  * "asm_short_slots_P" / "asm_long_slots_P" / "asm_vlong_slots_P" (P = 0 static, 1 dynamic matrix part: BSR blocks of the current pattern summed by
  * the one-lane / one-wavefront / 64-wavefront gather kernel, by the length of their contribution lists), "llt_path" / "llt_panel_rows" /
  * "llt_panels" / "llt_fronts" (the last DirectLLT solve: 0 dense, 1 band, 2 multifrontal, -1 none yet; block rows per panel — multifrontal: of the

@@ -65,10 +65,37 @@ int mistark_contact_count_intersections(mistark_ctx* ctx, double dt, int64_t* n_
 
 /* Continuous collision detection: largest fraction t in (0, 1] of the current Newton direction along which no collision pair's distance falls
  * below (1 - conservative_rescaling) of its distance at the line search's start (additive CCD on linear vertex trajectories: positions x0 + dt v1
- * at the engine's DoFs u and at u + du; rigid-body rotation is linearised between the two). Meaningful inside a max_allowed_step callback.
+ * at the engine's DoFs u and at u + du; rigid-body rotation is linearised between the two — mistark_contact_max_step_ex below has a mode that is sound
+ * for the true rotation). Meaningful inside a max_allowed_step callback.
  * Returns 1 when collisions are disabled or nothing moves. A sharded context returns an error. n_candidates: pairs whose swept boxes overlap
  * (nullable). Leaves the installed tables and the detection caches alone. */
 int mistark_contact_max_step(mistark_ctx* ctx, double dt, double conservative_rescaling, double* max_step, int64_t* n_candidates);
+
+/* The same query with the choice of how rigid bodies move, and along a direction of the caller's.
+ *   rigid_mode 0 (linear): mistark_contact_max_step itself — rigid vertices on the chord between their positions at u and at u + du.
+ *   rigid_mode 1 (curved): sound for the true motion. A rigid vertex follows t -> t0 + dt (v + t dv) + R1(q0, w + t dw, dt) x_loc, which leaves the chord
+ *     over [0, tau] by at most  delta(tau) = min((7/16) r (phi tau)^2, 2 r),  r = |x_loc|, phi = dt |dw|  (derivation: DESIGN.md section 4). The chord query
+ *     runs on the padded distance d~ = d - pad, pad = largest delta on one side of the pair + largest on the other (0.0 for deformable vertices and for
+ *     dw == 0): additive CCD with per-pair minimum separation pad. While a surviving pair is pad-bound (pad > d(0) / 2: the pad, not the motion, would stop
+ *     the step) the query is repeated on [0, tau / 2] with the end point placed anew at u + (tau / 2) du, which quarters every pad; at most max_rounds
+ *     rounds (>= 1), each one more pass of the kernels and one more read-back. max_step = tau * (the last round's result).
+ *     Guarantee: for every t in [0, max_step] the true rigid and deformable motion keeps every candidate pair apart (d > 0), and at max_step the pair
+ *     that limits it keeps a gap of (1 - conservative_rescaling) (d(0) - pad). A pair that after the last round still has d(0) <= pad gives max_step = 0: the line search
+ *     then fails and the caller is expected to shorten dt (which shrinks phi) — conservative, never unsound. With no rotation change (dw == 0 for every body,
+ *     or no rigid mesh) max_step, n_candidates and rounds == 1 are rigid_mode 0's bit for bit.
+ * du: NULL = the engine's current Newton direction (meaningful inside a max_allowed_step callback); else a host array of mistark_ndofs doubles in the
+ * layout of the DoF vector, which makes the query usable outside a Newton solve. The engine's own direction is not touched.
+ * Errors: sharded context, conservative_rescaling outside (0, 1], rigid_mode not 0 or 1, max_rounds < 1. Counters: "ccd_rounds", "ccd_pad_bound_pairs". */
+typedef struct mistark_ccd_result
+{
+    double max_step;          /* in [0, 1] */
+    double tau;               /* length of the last round's interval: 2^-(rounds - 1) */
+    double max_pad;           /* largest pad over the last round's candidates */
+    int64_t n_candidates;     /* pairs whose (padded) swept boxes overlap, last round */
+    int64_t rounds;           /* passes made (0: no collision mesh) */
+    int64_t pad_bound_pairs;  /* surviving pairs of the last round with pad > d(0) / 2 (0 unless the rounds ran out) */
+} mistark_ccd_result;
+int mistark_contact_max_step_ex(mistark_ctx* ctx, double dt, double conservative_rescaling, int rigid_mode, int max_rounds, const double* du, mistark_ccd_result* out);
 
 /* Parity access: rows of one table (by potential name, e.g. "contact_d_d_pt_pt_cubic"); conn == NULL queries n_rows/stride. */
 int mistark_contact_get_table(mistark_ctx* ctx, const char* potential, int32_t* conn, int32_t* n_rows, int32_t* stride);

@@ -175,8 +175,16 @@ int mistark_sim_disable_collision(mistark_sim* sim, int group_a, int group_b);
 int mistark_sim_get_contact_info(mistark_sim* sim, double* contact_stiffness, int64_t* n_contacts, int64_t* n_friction_contacts, int64_t* n_detections);
 /* Continuous collision detection (off by default; not in the reference): enabled, every Newton line search is bounded so that no collision
  * pair's distance falls below (1 - conservative_rescaling) of its start value along the step (one max_allowed_step callback calling
- * mistark_contact_max_step; rigid-body rotation linearised). Off, no callback is registered. */
+ * mistark_contact_max_step; rigid-body rotation linearised unless mistark_sim_set_contact_ccd_rigid says otherwise). Off, no callback is registered. */
 int mistark_sim_set_contact_ccd(mistark_sim* sim, int enabled, double conservative_rescaling);
+/* How rigid bodies move in the CCD query (kept across mistark_sim_set_contact_ccd; no effect while CCD is off). mode 0, linear (the default): on the chord
+ * between their end positions, the query above unchanged. mode 1, curved: on their true rotating paths — mistark_contact_max_step_ex with rigid_mode 1,
+ * the chord padded by a proved bound of the path's deviation and the interval halved while the pad is what limits the step, max_rounds (>= 1, usually 4) passes at most.
+ * Then, for every fraction of the Newton step up to the one the line search is allowed, no candidate pair of the true motion touches. A query in which
+ * a pad still leaves some pair no gap after max_rounds allows no step: the line search fails and the step is repeated with a smaller time step, as any failed step is. */
+int mistark_sim_set_contact_ccd_rigid(mistark_sim* sim, int mode, int max_rounds);
+/* mode as set; passes of the CCD chain over all queries (>= queries), pairs left pad-bound when a query's rounds ran out, largest pad seen (nullable outputs) */
+int mistark_sim_get_ccd_rigid_info(mistark_sim* sim, int* mode, int64_t* n_rounds, int64_t* n_pad_bound_pairs, double* max_pad);
 /* CCD counters of the simulation: queries, queries that limited the step, candidate pairs of the last query, pairs skipped because they touch
  * at a line search's start, pairs stopped at the iteration cap, seconds spent in the queries (nullable outputs) */
 int mistark_sim_get_ccd_info(mistark_sim* sim, int64_t* n_queries, int64_t* n_limited, int64_t* last_candidates, int64_t* n_skipped, int64_t* n_capped, double* seconds);

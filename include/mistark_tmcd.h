@@ -63,6 +63,14 @@ int mistark_cd_get_intersections(mistark_cd* cd, int32_t* rows);
  * falls below (1 - conservative_rescaling) of its start value (additive CCD, minimum distance 0; 1 = no such pair). Pairs that touch at the
  * start are left to the intersection test. n_candidates: pairs whose swept boxes overlap. For a STARK application's add_max_allowed_step. */
 int mistark_cd_run_ccd(mistark_cd* cd, const double* const* x1, double conservative_rescaling, double* toi, int32_t* n_candidates);
+/* The same motion with every vertex allowed to leave its straight line by pad (one array per mesh, one non-negative value per vertex): additive CCD
+ * with a per-pair minimum separation. A pair's pad is the largest pad on one side plus the largest on the other; swept boxes are grown by their
+ * primitive's largest pad; everything runs on the padded distance d~ = d - pad: for all t <= toi every pair keeps d~ > 0, at toi it keeps
+ * d~ >= (1 - conservative_rescaling) d~(0). A pair whose pad leaves no gap at the start (0 < d(0) <= pad) gives toi = 0. n_pad_bound: surviving pairs
+ * with pad > d(0) / 2 (the pad, not the motion, limits them). With every pad 0.0 the result is mistark_cd_run_ccd's bit for bit. These are the
+ * kernels of mistark_contact_max_step_ex's curved rigid mode (mistark_contact.h), reachable without rigid bodies. */
+int mistark_cd_run_ccd_padded(mistark_cd* cd, const double* const* x1, const double* const* pad, double conservative_rescaling, double* toi, int32_t* n_candidates,
+                              int32_t* n_pad_bound);
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,12 @@ class ContactArrays(C.Structure):
     _fields_ = [(r, C.c_int32) for r in CONTACT_ROLES]
 
 
+class CcdResult(C.Structure):
+    """include/mistark_contact.h: mistark_ccd_result (mistark_contact_max_step_ex)."""
+    _fields_ = [("max_step", C.c_double), ("tau", C.c_double), ("max_pad", C.c_double), ("n_candidates", C.c_int64), ("rounds", C.c_int64),
+                ("pad_bound_pairs", C.c_int64)]
+
+
 class PcgInfo(C.Structure):
     _fields_ = [("converged", C.c_int32), ("n_iterations", C.c_int32), ("found_indefiniteness", C.c_int32), ("reserved", C.c_int32), ("error", C.c_double)]
 
@@ -137,6 +143,7 @@ def lib():
     L.mistark_contact_update_friction.argtypes = [p, C.POINTER(i64)]
     L.mistark_contact_count_intersections.argtypes = [p, C.c_double, C.POINTER(i64)]
     L.mistark_contact_max_step.argtypes = [p, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)]
+    L.mistark_contact_max_step_ex.argtypes = [p, C.c_double, C.c_double, C.c_int, C.c_int, p, C.POINTER(CcdResult)]
     L.mistark_contact_get_table.argtypes = [p, C.c_char_p, p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.mistark_contact_get_friction_data.argtypes = [p, C.c_char_p, p, p, p, p, C.POINTER(C.c_int32)]
     L.mistark_contact_get_vertices.argtypes = [p, p, C.POINTER(i64)]
@@ -355,6 +362,21 @@ class CollisionDetector:
         toi, n = C.c_double(), C.c_int32()
         self._ck(self.L.mistark_cd_run_ccd(self.h, ptrs, conservative_rescaling, C.byref(toi), C.byref(n)))
         return toi.value, n.value
+
+    def run_ccd_padded(self, x1, pad, conservative_rescaling=0.9):
+        """mistark_cd_run_ccd_padded: (toi, n_candidates, n_pad_bound) of the same motion with every vertex allowed to leave its straight line by its
+        pad (one array of non-negative values per mesh): additive CCD on the padded distances."""
+        import numpy as np
+        self.L.mistark_cd_run_ccd_padded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        ends = [np.ascontiguousarray(x, dtype=np.float64) for x in x1]
+        pads = [np.ascontiguousarray(q, dtype=np.float64).ravel() for q in pad]
+        if len(pads) != len(ends) or any(3 * len(q) != e.size for q, e in zip(pads, ends)):
+            raise ValueError("run_ccd_padded: one pad per vertex of every mesh")
+        ptrs = (C.c_void_p * max(len(ends), 1))(*[x.ctypes.data for x in ends])
+        pptrs = (C.c_void_p * max(len(pads), 1))(*[q.ctypes.data for q in pads])
+        toi, n, nb = C.c_double(), C.c_int32(), C.c_int32()
+        self._ck(self.L.mistark_cd_run_ccd_padded(self.h, ptrs, pptrs, conservative_rescaling, C.byref(toi), C.byref(n), C.byref(nb)))
+        return toi.value, n.value, nb.value
 
     def close(self):
         if self.h:

@@ -571,6 +571,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "ccd_queries") *out = contact_ccd_counter(c, 0);
     else if (n == "ccd_skipped_pairs") *out = contact_ccd_counter(c, 1);
     else if (n == "ccd_capped_pairs") *out = contact_ccd_counter(c, 2);
+    else if (n == "ccd_rounds") *out = contact_ccd_counter(c, 3);
+    else if (n == "ccd_pad_bound_pairs") *out = contact_ccd_counter(c, 4);
     // BSR blocks summed by each assembly kernel of the current pattern (part 0 static, 1 dynamic): k_assemble_gather(_split) / k_assemble_long /
     // k_assemble_vlong_part + _fold; host values of the pattern build
     else if (n == "asm_short_slots_0" || n == "asm_short_slots_1") { ensure_pattern(c); const BsrPart& m = c.part[n.back() - '0']; *out = m.nnzb - m.n_long - m.n_vlong; }

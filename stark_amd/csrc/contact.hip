@@ -27,6 +27,7 @@
 #include "../../include/mistark_contact.h"
 #include "contact_geom.hpp"
 #include "energies.hpp"
+#include "ccd_pad.hpp"
 #include "engine.hpp"
 #include "dist.hpp"
 
@@ -1002,6 +1003,7 @@ __global__ __launch_bounds__(CB) void k_route(ContactDev d, const uint64_t* __re
 constexpr int CCD_MAX_ITERATIONS = 10000;
 // slots of ContactSystem::ccd_counters besides those of a search ([0] candidate pairs, [48..51] box list, [56] sweep tasks)
 constexpr int CCD_N_SURV = 16, CCD_N_SKIPPED = 17, CCD_N_CAPPED = 18, CCD_TOI = 20;  // (CCD_TOI: two ints, the bits of a double)
+constexpr int CCD_N_PAD_BOUND = 19, CCD_MAX_PAD = 22;                                // (padded path; CCD_MAX_PAD: two ints, the bits of a double)
 // deformable: x0 + dt v; rigid body: integrate_loc_point as k_contact_vertices (rotation linearised between the two end points)
 __global__ __launch_bounds__(CB) void k_ccd_vertices(ContactDev d, const double* __restrict__ x0, const double* __restrict__ v1, const double* __restrict__ dv1,
                                                     const double* __restrict__ xloc, const double* __restrict__ rb_v1, const double* __restrict__ drb_v1,
@@ -1032,8 +1034,47 @@ __global__ __launch_bounds__(CB) void k_ccd_vertices(ContactDev d, const double*
     place(nullptr, nullptr, xa);
     place(drb_v1, drb_w1, xb);
 }
-// swept boxes: float, rounded outwards (as k_contact_aabbs), over both end points, no enlargement; points, triangles, edges
-__global__ __launch_bounds__(CB) void k_ccd_aabbs(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, float* __restrict__ aabb)
+// Curved rigid mode (contact_max_step_ex, rigid_mode 1): as k_ccd_vertices with the end point at u + tau du, plus pad_v = how far the vertex's true path
+// t -> t0 + dt (v + t dv) + R1(q0, w + t dw, dt) x_loc may leave the chord xa -> xb on [0, tau] (ccd_pad.hpp: delta(tau), one |dw| per body, r from
+// rb_xloc). +0.0 for deformable vertices and where dw == 0; tau == 1 places both end points with k_ccd_vertices' bits (1.0 * x == x).
+__global__ __launch_bounds__(CB) void k_ccd_vertices_curved(ContactDev d, const double* __restrict__ x0, const double* __restrict__ v1, const double* __restrict__ dv1,
+                                                           const double* __restrict__ xloc, const double* __restrict__ rb_v1, const double* __restrict__ drb_v1,
+                                                           const double* __restrict__ rb_w1, const double* __restrict__ drb_w1, const double* __restrict__ rb_t0,
+                                                           const double* __restrict__ rb_q0, double dt, double tau, double* __restrict__ xa, double* __restrict__ xb,
+                                                           double* __restrict__ pad_v)
+{
+    const int i = blockIdx.x * CB + threadIdx.x;
+    if (i >= d.n_v) return;
+    const int m = d.cv_mesh[i], s = d.cv_src[i];
+    if (d.mesh_kind[m] == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double v = v1[3 * s + k];
+            xa[3 * i + k] = x0[3 * s + k] + dt * v;
+            xb[3 * i + k] = x0[3 * s + k] + dt * (v + (dv1 ? tau * dv1[3 * s + k] : 0.0));
+        }
+        pad_v[i] = 0.0;
+        return;
+    }
+    const int b = d.mesh_idx[m];
+    const V3<double> xl(xloc[3 * s], xloc[3 * s + 1], xloc[3 * s + 2]);
+    auto place = [&](const double* dv, const double* dw, double* X) {
+        const V3<double> w(rb_w1[3 * b] + (dw ? tau * dw[3 * b] : 0.0), rb_w1[3 * b + 1] + (dw ? tau * dw[3 * b + 1] : 0.0), rb_w1[3 * b + 2] + (dw ? tau * dw[3 * b + 2] : 0.0));
+        const V3<double> r = rb_R1(rb_q0 + 4 * b, w, dt) * xl;
+        X[3 * i] = r.x + (rb_t0[3 * b] + dt * (rb_v1[3 * b] + (dv ? tau * dv[3 * b] : 0.0)));
+        X[3 * i + 1] = r.y + (rb_t0[3 * b + 1] + dt * (rb_v1[3 * b + 1] + (dv ? tau * dv[3 * b + 1] : 0.0)));
+        X[3 * i + 2] = r.z + (rb_t0[3 * b + 2] + dt * (rb_v1[3 * b + 2] + (dv ? tau * dv[3 * b + 2] : 0.0)));
+    };
+    place(nullptr, nullptr, xa);
+    place(drb_v1, drb_w1, xb);
+    const double phi = drb_w1 ? ccd_pad_phi(dt, drb_w1[3 * b], drb_w1[3 * b + 1], drb_w1[3 * b + 2]) : 0.0;
+    pad_v[i] = ccd_pad_vertex(xloc + 3 * s, phi, tau);
+}
+// swept boxes: float, rounded outwards (as k_contact_aabbs), over both end points, no enlargement; points, triangles, edges.
+// PAD: each box grown by the largest pad_v of the primitive's vertices before the rounding (x -+ 0.0 == x).
+template <bool PAD>
+__global__ __launch_bounds__(CB) void k_ccd_aabbs(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, const double* __restrict__ pad_v,
+                                                 float* __restrict__ aabb)
 {
     const int i = blockIdx.x * CB + threadIdx.x;
     const int n = d.n_v + d.n_t + d.n_e;
@@ -1051,6 +1092,12 @@ __global__ __launch_bounds__(CB) void k_ccd_aabbs(ContactDev d, const double* __
         v[0] = d.edge[2 * e]; v[1] = d.edge[2 * e + 1];
         nv = 2;
     }
+    double pad = 0.0;
+    if constexpr (PAD) {
+        pad = pad_v[v[0]];
+        if (nv > 1) pad = fmax(pad, pad_v[v[1]]);
+        if (nv > 2) pad = fmax(pad, pad_v[v[2]]);
+    }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         double lo = xa[3 * v[0] + k], hi = lo;
@@ -1060,6 +1107,10 @@ __global__ __launch_bounds__(CB) void k_ccd_aabbs(ContactDev d, const double* __
             hi = p > hi ? p : hi;
             lo = q < lo ? q : lo;
             hi = q > hi ? q : hi;
+        }
+        if constexpr (PAD) {
+            lo -= pad;
+            hi += pad;
         }
         aabb[6 * (size_t)i + k] = __double2float_rd(lo);
         aabb[6 * (size_t)i + 3 + k] = __double2float_ru(hi);
@@ -1122,24 +1173,44 @@ __device__ __forceinline__ double ccd_distance(const CcdPair& P)
     }
     return ::sqrt(edge_edge_sq_distance(type, P.x[0], P.x[1], P.x[2], P.x[3]));
 }
+// the pad of a pair (padded path): the largest pad_v on one side plus the largest on the other — a point of a triangle or an edge is a convex
+// combination of its vertices, so it leaves its chord by no more than the largest of their deviations
+__device__ __forceinline__ double ccd_pair_pad(const ContactDev& d, uint64_t key, const double* __restrict__ pad_v)
+{
+    const int a = (int)((key >> PRIM_BITS) & ((1u << PRIM_BITS) - 1)), b = (int)(key & ((1u << PRIM_BITS) - 1));
+    if (!((key >> 57) & 1)) return pad_v[a] + fmax(pad_v[d.tri[3 * b]], fmax(pad_v[d.tri[3 * b + 1]], pad_v[d.tri[3 * b + 2]]));
+    return fmax(pad_v[d.edge[2 * a]], pad_v[d.edge[2 * a + 1]]) + fmax(pad_v[d.edge[2 * b]], pad_v[d.edge[2 * b + 1]]);
+}
 // One lane per candidate: pairs that touch at the start (d = 0: the intersection test's business) are counted and skipped; a pair with
 // l_p <= eta d(0) cannot close eta of its gap within t <= 1 and is dropped. The rest is compacted (ballot + one atomic per wavefront) so that
 // the iterative kernel runs on pairs that all iterate. Also sets the time of impact to 1.
-__global__ __launch_bounds__(CB) void k_ccd_filter(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, double eta, const uint64_t* __restrict__ keys,
-                                                  int key_cap, int* __restrict__ counters, uint64_t* __restrict__ surv)
+// PAD: everything on the padded distance d~ = d - pad (additive CCD with minimum separation pad, per pair). A pair whose pad leaves no gap
+// (d~(0) <= 0) is kept whatever it does: k_ccd_accd reports t = 0 for it. Pad-bound pairs (kept, pad > d(0) / 2) are counted, one integer atomic
+// per wavefront; the largest pad over the candidates is kept as an integer maximum on the bits of a non-negative double, one per wavefront.
+template <bool PAD>
+__global__ __launch_bounds__(CB) void k_ccd_filter(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, const double* __restrict__ pad_v, double eta,
+                                                  const uint64_t* __restrict__ keys, int key_cap, int* __restrict__ counters, uint64_t* __restrict__ surv)
 {
     const int i = blockIdx.x * CB + threadIdx.x, lane = threadIdx.x & 63;
     const int n = min(counters[0], key_cap);
     if (i == 0) *reinterpret_cast<unsigned long long*>(counters + CCD_TOI) = (unsigned long long)__double_as_longlong(1.0);
     if ((i & ~63) >= n) return;  // (wave-uniform)
-    bool keep = false, touching = false;
+    bool keep = false, touching = false, bound = false;
+    double pad = 0.0;
     uint64_t key = 0;
     if (i < n) {
         key = keys[i];
         const CcdPair P = ccd_pair(d, key, xa, xb);
         const double d0 = ccd_distance(P);
         touching = !(d0 > 0.0);
-        keep = !touching && ccd_lp(P) > eta * d0;
+        if constexpr (!PAD) {
+            keep = !touching && ccd_lp(P) > eta * d0;
+        } else {
+            pad = ccd_pair_pad(d, key, pad_v);
+            const double g0 = d0 - pad;
+            keep = !touching && (!(g0 > 0.0) || ccd_lp(P) > eta * g0);
+            bound = keep && pad > 0.5 * d0;
+        }
     }
     const unsigned long long mk = __ballot(keep), mt = __ballot(touching);
     int base = 0;
@@ -1147,12 +1218,22 @@ __global__ __launch_bounds__(CB) void k_ccd_filter(ContactDev d, const double* _
     base = __shfl(base, 0, 64);
     if (keep) surv[base + __popcll(mk & ((1ull << lane) - 1ull))] = key;
     if (lane == 0 && mt) atomicAdd(&counters[CCD_N_SKIPPED], __popcll(mt));
+    if constexpr (PAD) {
+        const unsigned long long mb = __ballot(bound);
+        if (lane == 0 && mb) atomicAdd(&counters[CCD_N_PAD_BOUND], __popcll(mb));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pad = fmax(pad, __shfl_xor(pad, o, 64));
+        if (lane == 0 && pad > 0.0) atomicMax(reinterpret_cast<unsigned long long*>(counters + CCD_MAX_PAD), (unsigned long long)__double_as_longlong(pad));
+    }
 }
 // Additive CCD of the filter's survivors. t_c is the running minimum over all pairs (a relaxed read of the device scalar): a pair that passes
 // it cannot lower the minimum and stops. Each pair's sequence of advances does not depend on t_c, only where it stops, so the minimum is
 // the same whatever order the pairs finish in. Result: one 64-bit atomic min per wavefront on the bits of a non-negative double.
-__global__ __launch_bounds__(CB) void k_ccd_accd(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, double eta, const uint64_t* __restrict__ surv,
-                                                int* __restrict__ counters)
+// PAD: dist is the padded distance d~ = d - pad throughout (advance by eta d~ / l_p, stop on d~ < (1 - eta) d~(0)); a pair without a gap at the
+// start (d~(0) <= 0) reports 0. With pad == 0.0 every value is the unpadded one (d - 0.0 == d).
+template <bool PAD>
+__global__ __launch_bounds__(CB) void k_ccd_accd(ContactDev d, const double* __restrict__ xa, const double* __restrict__ xb, const double* __restrict__ pad_v, double eta,
+                                                const uint64_t* __restrict__ surv, int* __restrict__ counters)
 {
     unsigned long long* toi_bits = reinterpret_cast<unsigned long long*>(counters + CCD_TOI);
     const int n = counters[CCD_N_SURV];
@@ -1162,6 +1243,15 @@ __global__ __launch_bounds__(CB) void k_ccd_accd(ContactDev d, const double* __r
         CcdPair P = ccd_pair(d, surv[i], xa, xb);
         const double lp = ccd_lp(P);
         double dist = ccd_distance(P);
+        double pad = 0.0;
+        if constexpr (PAD) {
+            pad = ccd_pair_pad(d, surv[i], pad_v);
+            dist -= pad;
+            if (!(dist > 0.0)) {
+                best = 0.0;
+                continue;
+            }
+        }
         const double gap = (1.0 - eta) * dist;
         double t = 0.0;
         for (int it = 0;;) {
@@ -1170,6 +1260,7 @@ __global__ __launch_bounds__(CB) void k_ccd_accd(ContactDev d, const double* __r
 #pragma unroll
             for (int k = 0; k < 4; k++) P.x[k] = P.x[k] + step * P.dx[k];
             dist = ccd_distance(P);
+            if constexpr (PAD) dist -= pad;
             if (t > 0.0 && dist < gap) {  // hit: t is the last position known to keep (1 - eta) of the gap
                 best = t < best ? t : best;
                 break;
@@ -1274,6 +1365,9 @@ struct ContactSystem : BoxSweep
     DevBuf<int> ccd_counters;
     size_t ccd_key_cap = 0;
     int64_t n_ccd_queries = 0, n_ccd_skipped = 0, n_ccd_capped = 0;
+    // padded path (contact_max_step_ex in curved rigid mode, mistark_cd_run_ccd_padded): per-vertex pads, a caller's direction, rounds and pad-bound pairs so far
+    DevBuf<double> ccd_pad, ccd_du;
+    int64_t n_ccd_rounds = 0, n_ccd_pad_bound = 0;
     DevBuf<uint8_t> cub_tmp;
     DevBuf<TableDev> tables_dev;
     size_t key_cap = 0;
@@ -1295,6 +1389,8 @@ int64_t contact_searches(const Context& c, bool repeated) { return !c.contact ? 
 int64_t contact_ccd_counter(const Context& c, int which)
 {
     if (!c.contact) return 0;
+    if (which == 3) return c.contact->n_ccd_rounds;
+    if (which == 4) return c.contact->n_ccd_pad_bound;
     return which == 0 ? c.contact->n_ccd_queries : (which == 1 ? c.contact->n_ccd_skipped : c.contact->n_ccd_capped);
 }
 void contact_shared_rows(Context& c, std::vector<int32_t>& rows)
@@ -2009,14 +2105,20 @@ struct CcdResult
 {
     double toi = 1.0;
     int64_t n_candidates = 0;
+    int64_t n_pad_bound = 0;  // padded path: surviving pairs with pad > d(0) / 2
+    double max_pad = 0.0;     // padded path: largest pad over the candidates
 };
 // Largest fraction of the straight-line motion cs.ccd_xa -> cs.ccd_xb that keeps every candidate pair's distance above (1 - eta) of its start
 // value. Reads and writes only the CCD buffers: the installed tables, the barrier search's key lists, box list and caches are left as they are.
-CcdResult ccd_query(Context& c, ContactSystem& cs, ContactDev d, double eta)
+// pad_v (nullable, one per collision vertex): the padded path — the same chain on the distances minus the pairs' pads, boxes grown by the pads.
+CcdResult ccd_query(Context& c, ContactSystem& cs, ContactDev d, double eta, const double* pad_v = nullptr, bool first_round = true)
 {
     const int np = cs.n_v + cs.n_t + cs.n_e;
     cs.ccd_aabb.ensure(6 * (size_t)np);
-    hipLaunchKernelGGL(k_ccd_aabbs, dim3((np + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, cs.ccd_aabb.p);
+    if (pad_v)
+        hipLaunchKernelGGL(k_ccd_aabbs<true>, dim3((np + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, pad_v, cs.ccd_aabb.p);
+    else
+        hipLaunchKernelGGL(k_ccd_aabbs<false>, dim3((np + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, pad_v, cs.ccd_aabb.p);
     d.aabb = cs.ccd_aabb.p;
     d.X = cs.ccd_xa.p;
     d.broad_only = 0;
@@ -2032,10 +2134,17 @@ CcdResult ccd_query(Context& c, ContactSystem& cs, ContactDev d, double eta)
         sort_boxes(c, cs, cs.ccd_sweep, d, cs.ccd_xa.p, cs.ccd_counters.p);
         launch_sweep<true, false>(c, cs, cs.ccd_sweep, d, 0.0, cs.ccd_keys.p, cs.ccd_counters.p, cs.ccd_key_cap, false);
         // (both kernels take their lengths from the device: one read-back per query)
-        hipLaunchKernelGGL(k_ccd_filter, dim3((cap + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, eta,
-                           (const uint64_t*)cs.ccd_keys.p, cap, cs.ccd_counters.p, cs.ccd_surv.p);
-        hipLaunchKernelGGL(k_ccd_accd, dim3(std::min((cap + CB - 1) / CB, 2048)), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, eta,
-                           (const uint64_t*)cs.ccd_surv.p, cs.ccd_counters.p);
+        if (pad_v) {
+            hipLaunchKernelGGL(k_ccd_filter<true>, dim3((cap + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, pad_v, eta,
+                               (const uint64_t*)cs.ccd_keys.p, cap, cs.ccd_counters.p, cs.ccd_surv.p);
+            hipLaunchKernelGGL(k_ccd_accd<true>, dim3(std::min((cap + CB - 1) / CB, 2048)), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p,
+                               pad_v, eta, (const uint64_t*)cs.ccd_surv.p, cs.ccd_counters.p);
+        } else {
+            hipLaunchKernelGGL(k_ccd_filter<false>, dim3((cap + CB - 1) / CB), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p, pad_v, eta,
+                               (const uint64_t*)cs.ccd_keys.p, cap, cs.ccd_counters.p, cs.ccd_surv.p);
+            hipLaunchKernelGGL(k_ccd_accd<false>, dim3(std::min((cap + CB - 1) / CB, 2048)), dim3(CB), 0, c.stream, d, (const double*)cs.ccd_xa.p, (const double*)cs.ccd_xb.p,
+                               pad_v, eta, (const uint64_t*)cs.ccd_surv.p, cs.ccd_counters.p);
+        }
         fetch(c, h, cs.ccd_counters.p, sizeof(h));
         if (h[51] > cs.ccd_sweep.bp_cap) {  // the banded box list did not fit: grow and query again
             cs.ccd_sweep.bp_cap = h[51] + h[51] / 4;
@@ -2050,18 +2159,21 @@ CcdResult ccd_query(Context& c, ContactSystem& cs, ContactDev d, double eta)
     CcdResult r;
     std::memcpy(&r.toi, h + CCD_TOI, sizeof(double));
     r.n_candidates = h[0];
-    cs.n_ccd_queries++;
+    r.n_pad_bound = h[CCD_N_PAD_BOUND];
+    std::memcpy(&r.max_pad, h + CCD_MAX_PAD, sizeof(double));
+    if (first_round) cs.n_ccd_queries++;
     cs.n_ccd_skipped += h[CCD_N_SKIPPED];
     cs.n_ccd_capped += h[CCD_N_CAPPED];
     return r;
 }
 // the Newton direction's counterpart of a DoF-view array (nullptr: the array does not move along du)
-const double* du_view(Context& c, int id)
+const double* du_view(Context& c, int id, const double* given = nullptr)
 {
     if (id < 0) return nullptr;
     const Array& a = c.arrays[(size_t)id];
     if (a.dof_set < 0) return nullptr;
     const DofSet& s = c.dof_sets[(size_t)a.dof_set];
+    if (given) return given + s.offset;  // (a caller's direction, ndofs doubles on the device: contact_max_step_ex)
     return c.du.p && c.du.cap >= (size_t)(s.offset + s.n) ? c.du.p + s.offset : nullptr;
 }
 // collision vertices at u (the line search's start) and u + du (the engine's current DoFs and Newton direction)
@@ -2080,6 +2192,65 @@ CcdResult contact_max_step(Context& c, double dt, double eta)
                        arr_dev(c, cs.arr.rb_xloc), arr_dev(c, cs.arr.rb_v1), du_view(c, cs.arr.rb_v1), arr_dev(c, cs.arr.rb_w1), du_view(c, cs.arr.rb_w1),
                        arr_dev(c, cs.arr.rb_t0), arr_dev(c, cs.arr.rb_q0), dt, cs.ccd_xa.p, cs.ccd_xb.p);
     return ccd_query(c, cs, d, eta);
+}
+// mistark_contact_max_step_ex. rigid_mode 0: the query above (optionally along a caller's direction). rigid_mode 1: rigid vertices on their true curved
+// paths — the chord query padded by ccd_pad.hpp's deviation bound, repeated on [0, tau / 2] (end point re-placed, every pad quartered) while a surviving pair
+// is pad-bound, at most max_rounds rounds; one more pass of the chain and one more read-back per round.
+struct CcdExResult
+{
+    double max_step = 1.0, tau = 1.0, max_pad = 0.0;
+    int64_t n_candidates = 0, rounds = 0, n_pad_bound = 0;
+};
+CcdExResult contact_max_step_ex(Context& c, double dt, double eta, int rigid_mode, int max_rounds, const double* du_host)
+{
+    if (c.world > 1) throw Error("contact: mistark_contact_max_step_ex is not available on a sharded context");
+    ContactSystem& cs = CS(c);
+    if (!(eta > 0.0 && eta <= 1.0)) throw Error("contact: conservative_rescaling must lie in (0, 1]");
+    if (rigid_mode != 0 && rigid_mode != 1) throw Error("contact: rigid_mode must be 0 (linear) or 1 (curved)");
+    if (max_rounds < 1) throw Error("contact: max_rounds must be at least 1");
+    CcdExResult out;
+    if (cs.meshes.empty()) return out;
+    prepare(c);
+    upload_meshes(c, cs);
+    const double* du = nullptr;
+    if (du_host) {
+        cs.ccd_du.ensure((size_t)c.ndofs);
+        h2d_staged(c, cs.ccd_du.p, du_host, (size_t)c.ndofs * sizeof(double));
+        du = cs.ccd_du.p;
+    }
+    const ContactDev d = dev_view(c, cs);
+    cs.ccd_xa.ensure(3 * (size_t)cs.n_v);
+    cs.ccd_xb.ensure(3 * (size_t)cs.n_v);
+    if (rigid_mode == 0) {
+        hipLaunchKernelGGL(k_ccd_vertices, dim3((cs.n_v + CB - 1) / CB), dim3(CB), 0, c.stream, d, arr_dev(c, cs.arr.x0), arr_dev(c, cs.arr.v1), du_view(c, cs.arr.v1, du),
+                           arr_dev(c, cs.arr.rb_xloc), arr_dev(c, cs.arr.rb_v1), du_view(c, cs.arr.rb_v1, du), arr_dev(c, cs.arr.rb_w1), du_view(c, cs.arr.rb_w1, du),
+                           arr_dev(c, cs.arr.rb_t0), arr_dev(c, cs.arr.rb_q0), dt, cs.ccd_xa.p, cs.ccd_xb.p);
+        const CcdResult r = ccd_query(c, cs, d, eta);
+        out.max_step = r.toi;
+        out.n_candidates = r.n_candidates;
+        out.rounds = 1;
+        cs.n_ccd_rounds++;
+        return out;
+    }
+    cs.ccd_pad.ensure((size_t)cs.n_v);
+    double tau = 1.0;
+    for (int round = 1;; round++) {
+        hipLaunchKernelGGL(k_ccd_vertices_curved, dim3((cs.n_v + CB - 1) / CB), dim3(CB), 0, c.stream, d, arr_dev(c, cs.arr.x0), arr_dev(c, cs.arr.v1), du_view(c, cs.arr.v1, du),
+                           arr_dev(c, cs.arr.rb_xloc), arr_dev(c, cs.arr.rb_v1), du_view(c, cs.arr.rb_v1, du), arr_dev(c, cs.arr.rb_w1), du_view(c, cs.arr.rb_w1, du),
+                           arr_dev(c, cs.arr.rb_t0), arr_dev(c, cs.arr.rb_q0), dt, tau, cs.ccd_xa.p, cs.ccd_xb.p, cs.ccd_pad.p);
+        const CcdResult r = ccd_query(c, cs, d, eta, cs.ccd_pad.p, round == 1);
+        cs.n_ccd_rounds++;
+        out.max_step = tau * r.toi;
+        out.tau = tau;
+        out.max_pad = r.max_pad;
+        out.n_candidates = r.n_candidates;
+        out.rounds = round;
+        out.n_pad_bound = r.n_pad_bound;
+        if (r.n_pad_bound == 0 || round == max_rounds) break;
+        tau *= 0.5;
+    }
+    cs.n_ccd_pad_bound += out.n_pad_bound;
+    return out;
 }
 int find_table(const char* name)
 {
@@ -2131,7 +2302,7 @@ struct StandaloneDetector
 {
     Context c;
     std::vector<const double*> xm;
-    PinnedBuf<double> X, X1;  // (X1: end positions of mistark_cd_run_ccd)
+    PinnedBuf<double> X, X1, P;  // (X1: end positions of mistark_cd_run_ccd; P: pads of mistark_cd_run_ccd_padded)
     std::vector<int32_t> rows[6], et_rows, bp_rows[2];  // (bp_rows: the last broad-phase listing, point-triangle | edge-edge, 4 columns)
     std::vector<double> dist[6];
     PinnedBuf<uint64_t> keys;
@@ -2575,6 +2746,45 @@ int mistark_cd_run_ccd(mistark_cd* cd, const double* const* x1, double conservat
     if (n_candidates) *n_candidates = (int32_t)r.n_candidates;
     CD_END(0)
 }
+int mistark_cd_run_ccd_padded(mistark_cd* cd, const double* const* x1, const double* const* pad, double conservative_rescaling, double* toi, int32_t* n_candidates,
+                              int32_t* n_pad_bound)
+{
+    CD_BEGIN
+    StandaloneDetector& D = cd->D;
+    Context& c = D.c;
+    ContactSystem& cs = CS(c);
+    MS_CHECK(hipSetDevice(c.device));
+    if (toi) *toi = 1.0;
+    if (n_candidates) *n_candidates = 0;
+    if (n_pad_bound) *n_pad_bound = 0;
+    if (!(conservative_rescaling > 0.0 && conservative_rescaling <= 1.0)) throw Error("cd: conservative_rescaling must lie in (0, 1]");
+    if (cs.meshes.empty()) return 0;
+    if (!x1 || !pad) throw Error("cd: null end positions or pads");
+    for (size_t g = 0; g < cs.meshes.size(); g++) {
+        if (!x1[g] || !pad[g]) throw Error("cd: null end positions or pads of mesh " + std::to_string(g));
+        for (int i = 0; i < cs.meshes[g].n_v; i++)
+            if (!(pad[g][i] >= 0.0)) throw Error("cd: pads must be non-negative numbers");
+    }
+    if (cs.meshes_dirty) upload_meshes(c, cs);
+    cd_gather_positions(D);
+    D.X1.resize(D.X.size());
+    D.P.resize((size_t)cs.n_v);
+    for (size_t g = 0; g < cs.meshes.size(); g++) {
+        std::memcpy(D.X1.data() + 3 * (size_t)cs.meshes[g].v_off, x1[g], 3 * (size_t)cs.meshes[g].n_v * sizeof(double));
+        std::memcpy(D.P.data() + (size_t)cs.meshes[g].v_off, pad[g], (size_t)cs.meshes[g].n_v * sizeof(double));
+    }
+    cs.ccd_xa.ensure(D.X.size());
+    cs.ccd_xb.ensure(D.X.size());
+    cs.ccd_pad.ensure(std::max<size_t>(D.P.size(), 1));
+    MS_CHECK(hipMemcpyAsync(cs.ccd_xa.p, D.X.data(), D.X.size() * sizeof(double), hipMemcpyHostToDevice, c.stream));
+    MS_CHECK(hipMemcpyAsync(cs.ccd_xb.p, D.X1.data(), D.X1.size() * sizeof(double), hipMemcpyHostToDevice, c.stream));
+    MS_CHECK(hipMemcpyAsync(cs.ccd_pad.p, D.P.data(), D.P.size() * sizeof(double), hipMemcpyHostToDevice, c.stream));
+    const CcdResult r = ccd_query(c, cs, cd_view(D), conservative_rescaling, cs.ccd_pad.p);  // (its read-back waits for the uploads)
+    if (toi) *toi = r.toi;
+    if (n_candidates) *n_candidates = (int32_t)r.n_candidates;
+    if (n_pad_bound) *n_pad_bound = (int32_t)r.n_pad_bound;
+    CD_END(0)
+}
 int mistark_cd_get_intersections(mistark_cd* cd, int32_t* rows)
 {
     CD_BEGIN
@@ -2687,6 +2897,20 @@ int mistark_contact_max_step(mistark_ctx* ctx, double dt, double conservative_re
     const CcdResult r = contact_max_step(ctx->c, dt, conservative_rescaling);
     if (max_step) *max_step = r.toi;
     if (n_candidates) *n_candidates = r.n_candidates;
+    CAPI_END(0)
+}
+int mistark_contact_max_step_ex(mistark_ctx* ctx, double dt, double conservative_rescaling, int rigid_mode, int max_rounds, const double* du, mistark_ccd_result* out)
+{
+    CAPI_BEGIN
+    const CcdExResult r = contact_max_step_ex(ctx->c, dt, conservative_rescaling, rigid_mode, max_rounds, du);
+    if (out) {
+        out->max_step = r.max_step;
+        out->tau = r.tau;
+        out->max_pad = r.max_pad;
+        out->n_candidates = r.n_candidates;
+        out->rounds = r.rounds;
+        out->pad_bound_pairs = r.n_pad_bound;
+    }
     CAPI_END(0)
 }
 int mistark_contact_get_table(mistark_ctx* ctx, const char* potential, int32_t* conn, int32_t* n_rows, int32_t* stride)

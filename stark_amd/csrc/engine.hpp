@@ -684,7 +684,7 @@ void static_graph_order(Context& c, std::vector<int32_t>& rows_in_order);  // sh
 void ensure_pattern(Context& c);
 void contact_destroy(struct ContactSystem* cs);
 int64_t contact_searches(const Context& c, bool repeated);  // counters "contact_searches" / "contact_repeated_searches"
-int64_t contact_ccd_counter(const Context& c, int which);   // counters "ccd_queries" (0) / "ccd_skipped_pairs" (1) / "ccd_capped_pairs" (2)
+int64_t contact_ccd_counter(const Context& c, int which);   // counters "ccd_queries" (0) / "ccd_skipped_pairs" (1) / "ccd_capped_pairs" (2) / "ccd_rounds" (3) / "ccd_pad_bound_pairs" (4)
 int64_t contact_sharded_searches(const Context& c);  // searches of a sharded problem whose sweep was dealt out to the ranks (contact.hip)
 void contact_shared_rows(Context& c, std::vector<int32_t>& rows);  // contact.hip
 // contact.hip: what the contact report reads of the detector — the collision meshes on the device, the sorted key list of the installed barrier tables and

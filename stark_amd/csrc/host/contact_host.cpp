@@ -202,6 +202,8 @@ void EnergyFrictionalContact::set_ccd(const CCDParams& p)
 {
     if (p.enabled && !(p.conservative_rescaling > 0.0 && p.conservative_rescaling <= 1.0))
         throw std::runtime_error("EnergyFrictionalContact::set_ccd: conservative_rescaling must lie in (0, 1]");
+    if (p.rigid_mode != 0 && p.rigid_mode != 1) throw std::runtime_error("EnergyFrictionalContact::set_ccd: rigid_mode must be 0 (linear) or 1 (curved)");
+    if (p.max_rounds < 1) throw std::runtime_error("EnergyFrictionalContact::set_ccd: max_rounds must be at least 1");
     ccd = p;
     auto& cbs = stark.callbacks->newton->max_allowed_step;
     if (p.enabled && ccd_callback < 0) {
@@ -218,7 +220,18 @@ double EnergyFrictionalContact::_max_allowed_step()
     const auto t0 = std::chrono::steady_clock::now();
     double t = 1.0;
     int64_t n = 0;
-    stark.check(mistark_contact_max_step(stark.ctx, stark.dt, ccd.conservative_rescaling, &t, &n));
+    if (ccd.rigid_mode == 0) {
+        stark.check(mistark_contact_max_step(stark.ctx, stark.dt, ccd.conservative_rescaling, &t, &n));
+        ccd_info.rounds++;
+    } else {
+        mistark_ccd_result r{};
+        stark.check(mistark_contact_max_step_ex(stark.ctx, stark.dt, ccd.conservative_rescaling, ccd.rigid_mode, ccd.max_rounds, nullptr, &r));
+        t = r.max_step;
+        n = r.n_candidates;
+        ccd_info.rounds += r.rounds;
+        ccd_info.pad_bound_pairs += r.pad_bound_pairs;
+        ccd_info.max_pad = std::max(ccd_info.max_pad, r.max_pad);
+    }
     ccd_info.queries++;
     if (t < 1.0) ccd_info.limited++;
     ccd_info.last_candidates = n;

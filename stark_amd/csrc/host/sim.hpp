@@ -679,11 +679,18 @@ public:
     {
         bool enabled = false;
         double conservative_rescaling = 0.9;
+        // how rigid bodies move in the query (mistark_contact_max_step_ex): 0 = on the chord between their end positions (the default: the query of
+        // mistark_contact_max_step itself), 1 = on their true curved paths (chord padded by the proved deviation bound, up to max_rounds halvings)
+        int rigid_mode = 0;
+        int max_rounds = 4;
     };
     struct CCDInfo
     {
         int64_t queries = 0, limited = 0, last_candidates = 0;
         double time = 0.0;  // seconds in the queries
+        // curved rigid mode: passes over all queries, pad-bound pairs left when the rounds ran out, largest pad seen
+        int64_t rounds = 0, pad_bound_pairs = 0;
+        double max_pad = 0.0;
     };
     struct Handler
     {

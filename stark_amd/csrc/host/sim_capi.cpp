@@ -662,7 +662,29 @@ int mistark_sim_get_contact_info(mistark_sim* s, double* k, int64_t* n_contacts,
 int mistark_sim_set_contact_ccd(mistark_sim* s, int enabled, double conservative_rescaling)
 {
     SIM_BEGIN
-    s->sim->interactions->contact->set_ccd(EnergyFrictionalContact::CCDParams{enabled != 0, conservative_rescaling});
+    EnergyFrictionalContact::CCDParams p = s->sim->interactions->contact->get_ccd();  // (the rigid mode is kept)
+    p.enabled = enabled != 0;
+    p.conservative_rescaling = conservative_rescaling;
+    s->sim->interactions->contact->set_ccd(p);
+    SIM_END
+}
+int mistark_sim_set_contact_ccd_rigid(mistark_sim* s, int mode, int max_rounds)
+{
+    SIM_BEGIN
+    EnergyFrictionalContact::CCDParams p = s->sim->interactions->contact->get_ccd();
+    p.rigid_mode = mode;
+    p.max_rounds = max_rounds;
+    s->sim->interactions->contact->set_ccd(p);
+    SIM_END
+}
+int mistark_sim_get_ccd_rigid_info(mistark_sim* s, int* mode, int64_t* n_rounds, int64_t* n_pad_bound_pairs, double* max_pad)
+{
+    SIM_BEGIN
+    const EnergyFrictionalContact::CCDInfo& i = s->sim->interactions->contact->ccd_info;
+    if (mode) *mode = s->sim->interactions->contact->get_ccd().rigid_mode;
+    if (n_rounds) *n_rounds = i.rounds;
+    if (n_pad_bound_pairs) *n_pad_bound_pairs = i.pad_bound_pairs;
+    if (max_pad) *max_pad = i.max_pad;
     SIM_END
 }
 int mistark_sim_get_ccd_info(mistark_sim* s, int64_t* n_queries, int64_t* n_limited, int64_t* last_candidates, int64_t* n_skipped, int64_t* n_capped, double* seconds)

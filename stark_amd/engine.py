@@ -176,6 +176,23 @@ class Engine:
         self._ck(self.L.mistark_contact_max_step(self.h, dt, conservative_rescaling, C.byref(t), C.byref(n)))
         return t.value, n.value
 
+    CCD_RIGID_MODES = ("linear", "curved")
+
+    def contact_max_step_ex(self, dt, conservative_rescaling=0.9, rigid_mode="linear", max_rounds=4, du=None) -> dict:
+        """mistark_contact_max_step_ex: the CCD query with rigid bodies on their chords ("linear") or on their true curved paths ("curved"), along the
+        current Newton direction (du None) or a given one (ndofs doubles). Returns max_step, n_candidates, rounds, tau, pad_bound_pairs, max_pad."""
+        if rigid_mode not in self.CCD_RIGID_MODES:
+            raise ValueError("contact_max_step_ex: rigid_mode must be one of %s, not %r" % (self.CCD_RIGID_MODES, rigid_mode))
+        ptr = None
+        if du is not None:
+            du = np.ascontiguousarray(du, dtype=np.float64)
+            if du.size != self.ndofs:
+                raise ValueError("contact_max_step_ex: du has %d entries, the engine %d DoFs" % (du.size, self.ndofs))
+            ptr = du.ctypes.data
+        r = capi.CcdResult()
+        self._ck(self.L.mistark_contact_max_step_ex(self.h, dt, conservative_rescaling, self.CCD_RIGID_MODES.index(rigid_mode), int(max_rounds), ptr, C.byref(r)))
+        return dict(max_step=r.max_step, n_candidates=r.n_candidates, rounds=r.rounds, tau=r.tau, pad_bound_pairs=r.pad_bound_pairs, max_pad=r.max_pad)
+
     def contact_table(self, name: str) -> np.ndarray:
         n, st = C.c_int32(), C.c_int32()
         self._ck(self.L.mistark_contact_get_table(self.h, name.encode(), None, C.byref(n), C.byref(st)))

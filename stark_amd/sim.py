@@ -131,6 +131,8 @@ def _lib():
         L.mistark_sim_set_contact_ccd.argtypes = [p, C.c_int, C.c_double]
         I64 = C.POINTER(C.c_int64)
         L.mistark_sim_get_ccd_info.argtypes = [p, I64, I64, I64, I64, I64, D]
+        L.mistark_sim_set_contact_ccd_rigid.argtypes = [p, C.c_int, C.c_int]
+        L.mistark_sim_get_ccd_rigid_info.argtypes = [p, C.POINTER(C.c_int), I64, I64, D]
         L.mistark_sim_record_forces.argtypes = [p, C.c_char_p]
         L.mistark_sim_get_forces.argtypes = [p, C.c_int, p, p]
         L.mistark_sim_record_stress.argtypes = [p, C.c_int]
@@ -437,6 +439,21 @@ class Simulation:
         t = C.c_double()
         self._ck(self.L.mistark_sim_get_ccd_info(self.h, C.byref(q), C.byref(lim), C.byref(cand), C.byref(sk), C.byref(cap), C.byref(t)))
         return dict(queries=q.value, limited=lim.value, last_candidates=cand.value, skipped_pairs=sk.value, capped_pairs=cap.value, seconds=t.value)
+
+    CCD_RIGID_MODES = ("linear", "curved")
+
+    def set_contact_ccd_rigid(self, mode="curved", max_rounds=4):
+        """How rigid bodies move in the CCD query: "linear" (the default) on the chord between their end positions, "curved" on their true rotating
+        paths (the chord padded by a proved deviation bound, halved up to max_rounds times while the pad limits the step). Kept across set_contact_ccd;
+        no effect while CCD is off."""
+        if mode not in self.CCD_RIGID_MODES:
+            raise ValueError("set_contact_ccd_rigid: mode must be one of %s, not %r" % (self.CCD_RIGID_MODES, mode))
+        self._ck(self.L.mistark_sim_set_contact_ccd_rigid(self.h, self.CCD_RIGID_MODES.index(mode), int(max_rounds)))
+
+    def ccd_rigid_info(self):
+        mode, r, pb, mp = C.c_int(), C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self.L.mistark_sim_get_ccd_rigid_info(self.h, C.byref(mode), C.byref(r), C.byref(pb), C.byref(mp)))
+        return dict(mode=self.CCD_RIGID_MODES[mode.value], rounds=r.value, pad_bound_pairs=pb.value, max_pad=mp.value)
 
     def prescribe_inside_aabb(self, point_set, center, dim, stiffness, tolerance=0.0) -> int:
         return self._ck(self.L.mistark_sim_prescribe_inside_aabb(self.h, point_set, _d3(center), _d3(dim), stiffness, tolerance))
