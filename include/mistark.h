@@ -205,6 +205,36 @@ int mistark_inertia_budget(mistark_ctx* ctx, int potential, const double about[3
  * rigid-body potential, J1 = R(q1) J_loc R(q1)^T; the item count is 1. */
 int mistark_rigid_budget(mistark_ctx* ctx, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3], double* out);
 
+/* ---- constraint report -----------------------------------------------------------------------------------------------------
+ * What the seventeen penalty-constraint potentials (EnergyPrescribedPositions, the five EnergyAttachments_*, the eleven rb_constraint_*) hold and carry at
+ * the current DoFs: per row the violation, the reaction, force and torque on side a, the two anchors, the energy and tolerance flags; per group counts, the
+ * worst row, the resultant, the moment and the energy. A pipeline of its own beside mistark_eval, like the readouts above: it writes only buffers of its
+ * own, uses no floating-point atomics and launches nothing unless it is called. The group sums run over fixed chunks of each group's row list in list order
+ * and through a fixed tree: two reports of one state give the same bits. Refused, with the cause in the message: sharded contexts (single-rank accessor),
+ * registration-only contexts, any other potential (by name), user-defined potentials, bad ids, n_groups not larger than the largest group id of the table,
+ * a negative or non-finite tolerance. The group of a row is the connectivity entry it reads its stiffness with: column 2 for prescribed positions, column 0
+ * for EnergyAttachments_d_d_p_p, column 1 for the other attachments, column 0 (the constraint itself) for every rigid-body kind. State: x1 = x0 + dt v1,
+ * bodies at t1 = t0 + dt v1, q1 = normalize(q0 + dt/2 (0, w1) q0), velocities v1, w1.
+ * Row record, 16 doubles:
+ *   0 violation (m, deg, m/s or deg/s by potential; signed for distances, distance limits, the damped spring and the velocity controllers; prescribed
+ *     positions and attachments: the distance |d| of the two material points) | 1 reaction (N or N m; prescribed positions and attachments: k |d|)
+ *   2..4 force on side a (the first party in the potential's name; the rigid body of rb_d), -dE/dx of its anchor; zero for direction-type rows
+ *   5..7 torque on side a about its centre of mass; zero when side a is deformable | 8..10 anchor (point-type) or unit direction of side a
+ *   11..13 anchor or direction of side b, or the global target (velocity controllers: 8..10 the axis, 11..13 the relative velocity of b)
+ *   14 energy of the row as the potential evaluates it | 15 flags: +1 active, +2 |violation| > tolerance of the row's group, +4 out of range
+ *   Inactive rows (is_active off, a limit not engaged) report 0 and 8..13 and zeros elsewhere.
+ * aux[row][2]: the damped spring's damper (relative velocity along the axis, -damping * that); zeros for every other kind.
+ * ids[row][4]: group, kind code 0..16 (the seventeen in registry order), block row of side a's first DoF block, of side b's or -1.
+ * Group record, 12 doubles: 0 rows | 1 active rows | 2 rows beyond tolerance | 3 largest |violation| | 4 position in the group's list (table order) of the
+ *   first row attaining it, -1 for a group without rows | 5..7 sum of 2..4 | 8..10 moment about `about`: sum of (anchor_a - about) x f, direction-type kinds
+ *   and the linear velocity controller: sum of 5..7 | 11 energy sum */
+/* tolerance: [n_groups] or NULL (then n_groups may be 0 and no row is flagged beyond tolerance). All output pointers may be NULL (n_rows and kind alone: a
+ * size query, nothing is launched). An empty table launches nothing and reports zero rows. */
+int mistark_potential_constraint_report(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, double* out, double* aux, int32_t* ids, int64_t* n_rows,
+                                        int32_t* kind);
+/* out[g][12], g < n_groups; a declared group without rows reports zeros with -1 in slot 4. */
+int mistark_constraint_group_report(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, const double about[3], double* out);
+
 /* ---- projection + assembly ------------------------------------------------------------------------------------------ */
 /* ElementHessians::project_to_PD_inplace__all / project_to_PD_for_update__selectively (ElementHessians.cpp:48-67,79-182;
  * project_to_PD.cpp:12-32). active_blocks: NULL = all elements, else ndofs/3 flags; only not-yet-projected elements
@@ -420,7 +450,8 @@ int mistark_sync(mistark_ctx* ctx);
  * calls that launched, rows of the last nodal readout summed by a whole wavefront), "budget_readouts" / "budget_chunks" (budget readout calls that
  * launched, chunks of the element list the last inertia budget was summed in), "contact_reports" / "contact_report_long_rows" (contact report calls
  * that launched, mistark_contact.h; collision vertices of the last report summed by a whole wavefront), "friction_reports" / "friction_report_long_rows"
- * (the same two for the friction report). */
+ * (the same two for the friction report), "constraint_reports" / "constraint_report_chunks" (constraint report calls that launched, chunks the last group
+ * report was summed in). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

@@ -248,6 +248,17 @@ int mistark_sim_record_budget(mistark_sim* sim, int enabled, const double about[
  * records [n_objects x 13]; inertia groups in group order, then bodies. time: the simulation time of the accepted step. */
 int mistark_sim_get_budget(mistark_sim* sim, int32_t* n_potentials, int32_t* n_objects, int64_t* names_bytes, int64_t* labels_bytes, double* time, char* names,
                            double* energies, char* labels, int32_t* kinds, double* records);
+/* Constraint recording (off by default; not in the reference), at the same place inside the step and before the callbacks of an accepted step (the
+ * stiffness reported is the one the step was solved with): one constraint report (mistark.h "constraint report": row records of 16 doubles, aux, ids,
+ * group records of 12 doubles with the moment about `about`, NULL = the origin) per registered constraint potential, with the tolerances the host
+ * tables hold (a table whose tolerances are all the largest double: none, no row is flagged). Results stay on the device until they are asked for. With
+ * recording off nothing is launched or allocated. */
+int mistark_sim_record_constraints(mistark_sim* sim, int enabled, const double about[3]);
+/* The report of one kind (0..16: the seventeen in registry order) at the last accepted step. Every output is nullable; a first call with the buffers
+ * NULL gives the sizes and downloads nothing. present: 0 when the scene registers no potential of the kind (everything else is then 0).
+ * rows [n_rows x 16], aux [n_rows x 2], ids [n_rows x 4], groups [n_groups x 12], tolerance [n_groups] (written when has_tolerance is 1). */
+int mistark_sim_get_constraints(mistark_sim* sim, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, int32_t* has_tolerance, double* time, double* rows,
+                                double* aux, int32_t* ids, double* groups, double* tolerance);
 /* Contact recording (off by default; not in the reference), at the same place inside the step: one contact report of the end-of-step state
  * (mistark_contact.h "contact report": the rows of the installed barrier tables, the vertex records, the group-pair records), after the Newton callbacks
  * that precede an evaluation, so that the installed tables are that state's. Results stay on the device until they are asked for. With recording off

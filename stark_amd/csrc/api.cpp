@@ -584,6 +584,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "stress_long_rows") *out = stress_long_rows(c);
     else if (n == "budget_readouts") *out = c.n_budget_readouts;
     else if (n == "budget_chunks") *out = c.n_budget_chunks;
+    else if (n == "constraint_reports") *out = c.n_constraint_reports;
+    else if (n == "constraint_report_chunks") *out = c.n_constraint_chunks;
     else if (n == "contact_reports") *out = c.n_contact_reports;
     else if (n == "contact_report_long_rows") *out = contact_report_long_rows(c);
     else if (n == "friction_reports") *out = c.n_friction_reports;
@@ -739,6 +741,20 @@ int mistark_nodal_stress(mistark_ctx* ctx, const int32_t* potentials, int32_t n,
 {
     API_BEGIN
     stress_nodal_host(ctx->c, potentials, n, out_host);
+    API_END(0)
+}
+
+// ---- constraint report (constraint_report.hip) ---------------------------------------------------------------------------
+int mistark_potential_constraint_report(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, double* out, double* aux, int32_t* ids, int64_t* n_rows, int32_t* kind)
+{
+    API_BEGIN
+    constraint_rows_host(ctx->c, potential, tolerance, n_groups, out, aux, ids, n_rows, kind);
+    API_END(0)
+}
+int mistark_constraint_group_report(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, const double about[3], double* out)
+{
+    API_BEGIN
+    constraint_groups_host(ctx->c, potential, tolerance, n_groups, about, out);
     API_END(0)
 }
 
@@ -1534,6 +1550,18 @@ int budget_record_rigid(mistark_ctx* ctx, int slot, int t0, int q0, int v1, int 
 {
     API_BEGIN
     budget_rigid(ctx->c, t0, q0, v1, w1, mass, J_loc, n_bodies, about, nullptr, slot);
+    API_END(0)
+}
+int constraint_record(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, const double about[3], int32_t* kind)
+{
+    API_BEGIN
+    constraint_record_kind(ctx->c, potential, tolerance, n_groups, about, kind);
+    API_END(0)
+}
+int constraint_fetch(mistark_ctx* ctx, int kind, double* out, double* aux, int32_t* ids, double* groups, int64_t* n_rows, int32_t* n_groups)
+{
+    API_BEGIN
+    constraint_fetch_kind(ctx->c, kind, out, aux, ids, groups, n_rows, n_groups);
     API_END(0)
 }
 int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n)

@@ -91,6 +91,15 @@ __global__ __launch_bounds__(BLOCK) void k_budget_rigid(const double* __restrict
     budget_store(acc, out + (size_t)BUDGET_REC * b);
 }
 
+// chunks of at most `chunk` terms over [first, first + count): (first term, number of terms) per chunk (shared with constraint_report.hip)
+void cut_chunks(std::vector<int32_t>& chunks, int64_t first, int64_t count, int chunk)
+{
+    for (int64_t at = 0; at < count; at += chunk) {
+        chunks.push_back((int32_t)(first + at));
+        chunks.push_back((int32_t)std::min<int64_t>(chunk, count - at));
+    }
+}
+
 namespace {
 // where a readout leaves its n doubles: the context's own buffer, or the host mirror's slot
 double* budget_target(Context& c, int slot, DevBuf<double>& own, size_t n)
@@ -121,14 +130,6 @@ void budget_finish(Context& c, int slot, const double* dev, bool launched, size_
     MS_CHECK(hipMemcpyAsync(out_host, dev, n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     MS_CHECK(hipStreamSynchronize(c.stream));
 }
-// chunks of at most BUDGET_CHUNK terms over [first, first + count)
-void cut_chunks(std::vector<int32_t>& chunks, int64_t first, int64_t count)
-{
-    for (int64_t at = 0; at < count; at += BUDGET_CHUNK) {
-        chunks.push_back((int32_t)(first + at));
-        chunks.push_back((int32_t)std::min<int64_t>(BUDGET_CHUNK, count - at));
-    }
-}
 // device pointer of an engine array with the stride and length a budget needs
 const double* budget_array(Context& c, int id, int stride, int64_t n_items, const char* role, const char* who)
 {
@@ -157,7 +158,7 @@ void budget_energies(Context& c, const int32_t* pots, int32_t n, double* out_hos
         chunk0.push_back((int32_t)(table.size() / 2));
         e_off.push_back(total);
         if (P.n_elem <= 0) continue;  // (empty tables launch nothing and report 0)
-        cut_chunks(table, total, P.n_elem);
+        cut_chunks(table, total, P.n_elem, BUDGET_CHUNK);
         total += P.n_elem;
     }
     if (total >= (1ll << 31)) throw Error(std::string(who) + ": too many elements");
@@ -212,7 +213,7 @@ void budget_inertia(Context& c, int pot, const double* about, int32_t n_groups, 
         std::vector<int32_t> table, chunk0;
         for (int g = 0; g < n_groups; g++) {
             chunk0.push_back((int32_t)(table.size() / 2));
-            cut_chunks(table, start[(size_t)g], start[(size_t)g + 1] - start[(size_t)g]);
+            cut_chunks(table, start[(size_t)g], start[(size_t)g + 1] - start[(size_t)g], BUDGET_CHUNK);
         }
         const int64_t n_chunks = (int64_t)table.size() / 2;
         chunk0.push_back((int32_t)n_chunks);

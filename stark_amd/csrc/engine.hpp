@@ -628,6 +628,32 @@ struct Context
     bool frr_stat_valid = false;
     int64_t n_friction_reports = 0;  // counter "friction_reports": calls that launched
 
+    // Constraint report (constraint_report.hip): the sixth pipeline beside eval(). Row records of one penalty-constraint potential at the current DoFs, field-major
+    // ([16][rows]), with aux [rows][2] and ids [rows][4]; the rows listed per group (stable) and cut into chunks of CONSTRAINT_CHUNK rows, one workgroup per
+    // chunk -> cnr_partial [chunk][12], one workgroup per group folds its chunks -> groups [group][12]. Nothing but these buffers is written. (The prefix is
+    // cnr_: cr_ is the contact report's.)
+    struct ConstraintReportSet       // cnr_set: what the accessors return; cnr_slots[kind code]: what the host mirror records inside a time step and keeps on the device
+    {
+        DevBuf<double> rec, aux, groups;
+        DevBuf<int32_t> ids;
+        int64_t n_rows = -1;         // -1: nothing yet
+        int32_t n_groups = 0;
+    };
+    ConstraintReportSet cnr_set;
+    std::vector<ConstraintReportSet> cnr_slots;
+    struct ConstraintPlan            // per potential: its rows group by group and the chunk table (per chunk: first item, item count; then per group (+1): first chunk)
+    {
+        DevBuf<uint32_t> items;
+        DevBuf<int32_t> chunks;
+        uint64_t conn_version = 0;
+        int n_elem = -1, n_groups = -1;
+        int64_t n_chunks = 0;
+    };
+    std::map<int, ConstraintPlan> cnr_plans;
+    DevBuf<double> cnr_tol, cnr_partial;
+    int64_t n_constraint_reports = 0;  // counter "constraint_reports": calls that launched
+    int64_t n_constraint_chunks = 0;   // counter "constraint_report_chunks": chunks of the last group report
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -795,6 +821,11 @@ void budget_energies(Context& c, const int32_t* pots, int32_t n, double* out_hos
 void budget_inertia(Context& c, int pot, const double* about, int32_t n_groups, double* out_host, int slot);
 void budget_rigid(Context& c, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double* about, double* out_host, int slot);
 void budget_fetch_slot(Context& c, int slot, double* out_host, int64_t n);
+// Constraint report (constraint_report.hip, records as constraint_report.hpp lays them out). Null outputs are skipped.
+void constraint_rows_host(Context& c, int pot, const double* tolerance, int32_t n_groups, double* out, double* aux, int32_t* ids, int64_t* n_rows, int32_t* kind);
+void constraint_groups_host(Context& c, int pot, const double* tolerance, int32_t n_groups, const double* about, double* out);
+void constraint_record_kind(Context& c, int pot, const double* tolerance, int32_t n_groups, const double* about, int32_t* kind);
+void constraint_fetch_kind(Context& c, int kind, double* out, double* aux, int32_t* ids, double* groups, int64_t* n_rows, int32_t* n_groups);
 int find_kind(const char* name);
 int kind_nb(int kind);
 int kind_nbind(int kind);

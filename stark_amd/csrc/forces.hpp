@@ -28,6 +28,9 @@ int budget_record_inertia(mistark_ctx* ctx, int slot, int potential, const doubl
 int budget_record_rigid(mistark_ctx* ctx, int slot, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double about[3]);
 // out[n] of slot `slot`
 int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n);
+// constraint report (constraint_report.hip): rows and groups of one potential into the set of its kind (0..16), kept on the device until fetched
+int constraint_record(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, const double about[3], int32_t* kind);
+int constraint_fetch(mistark_ctx* ctx, int kind, double* out, double* aux, int32_t* ids, double* groups, int64_t* n_rows, int32_t* n_groups);
 // contact report (contact_report.hip) of the current state into the device set of the host mirror; its three parts (null outputs are skipped, the counts
 // always come back)
 int contact_report_record(mistark_ctx* ctx);

@@ -98,25 +98,26 @@ void EnergyAttachments::register_potentials(mistark_ctx* ctx)
         id_stiffness[type] = B.b.back().array;
         B.add_id(stark.dt_array(), 1, -1);
     };
+    auto note = [&](int pot, int type) { stark.constraint_sources.push_back({pot, [this, type]() { return tolerance[type]; }}); };  // (constraint recording)
     if (!conn_p_p.empty()) {  // :17-35
         BindList B(ctx, stark);
         nodes(B, 1, 2);
         k_dt(B, PointPoint, 0);
-        B.potential("EnergyAttachments_d_d_p_p", conn_p_p);
+        note(B.potential("EnergyAttachments_d_d_p_p", conn_p_p), PointPoint);
     }
     if (!conn_p_e.empty()) {  // :37-60
         BindList B(ctx, stark);
         nodes(B, 2, 3);
         B.add(bary_p_e[0].data(), (int64_t)bary_p_e.size(), 2, 0);
         k_dt(B, PointEdge, 1);
-        B.potential("EnergyAttachments_d_d_p_e", conn_p_e);
+        note(B.potential("EnergyAttachments_d_d_p_e", conn_p_e), PointEdge);
     }
     if (!conn_p_t.empty()) {  // :62-85
         BindList B(ctx, stark);
         nodes(B, 2, 4);
         B.add(bary_p_t[0].data(), (int64_t)bary_p_t.size(), 3, 0);
         k_dt(B, PointTriangle, 1);
-        B.potential("EnergyAttachments_d_d_p_t", conn_p_t);
+        note(B.potential("EnergyAttachments_d_d_p_t", conn_p_t), PointTriangle);
     }
     if (!conn_e_e.empty()) {  // :87-111
         BindList B(ctx, stark);
@@ -124,7 +125,7 @@ void EnergyAttachments::register_potentials(mistark_ctx* ctx)
         B.add(bary_e_e_0[0].data(), (int64_t)bary_e_e_0.size(), 2, 0);
         B.add(bary_e_e_1[0].data(), (int64_t)bary_e_e_1.size(), 2, 0);
         k_dt(B, EdgeEdge, 1);
-        B.potential("EnergyAttachments_d_d_e_e", conn_e_e);
+        note(B.potential("EnergyAttachments_d_d_e_e", conn_e_e), EdgeEdge);
     }
     if (!conn_rb_d.empty()) {  // :113-135: k, dt, the point, the local point, then RigidBodyDynamics::get_x1's v1, w1, t0, q0_
         BindList B(ctx, stark);
@@ -136,7 +137,7 @@ void EnergyAttachments::register_potentials(mistark_ctx* ctx)
         B.add_id(rb->id_w1, 3, 2);
         B.add_id(rb->id_t0, 3, 2);
         B.add_id(rb->id_q0_, 4, 2);
-        B.potential("EnergyAttachments_rb_d", conn_rb_d);
+        note(B.potential("EnergyAttachments_rb_d", conn_rb_d), RigidDeformable);
     }
 }
 EnergyAttachments::Handler EnergyAttachments::new_handler(int type, const Params& params, int& group)

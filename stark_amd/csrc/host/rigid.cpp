@@ -27,9 +27,11 @@ struct Binder
     }
     void add_id(int id, int stride, int col) { b.push_back({id, stride, col}); }
     template <std::size_t N>
-    void potential(const char* name, const std::vector<std::array<int32_t, N>>& conn)
+    int potential(const char* name, const std::vector<std::array<int32_t, N>>& conn)
     {
-        stark.check(mistark_potential(ctx, name, conn.empty() ? nullptr : conn[0].data(), (int32_t)conn.size(), (int32_t)N, b.data(), (int32_t)b.size()));
+        const int id = mistark_potential(ctx, name, conn.empty() ? nullptr : conn[0].data(), (int32_t)conn.size(), (int32_t)N, b.data(), (int32_t)b.size());
+        stark.check(id);
+        return id;
     }
 };
 const Vec3 ZERO = {0.0, 0.0, 0.0};
@@ -365,15 +367,21 @@ void EnergyRigidBodyConstraints::register_potentials(mistark_ctx* ctx)
                 break;
             default: break;
         }
+        int pot = -1;
         if (KINDS[kind].two_bodies) {
-            B.potential(KINDS[kind].name, T.conn);
+            pot = B.potential(KINDS[kind].name, T.conn);
         } else {
             // one body: the reference's table is {idx, rb} (EnergyRigidBodyConstraints.cpp:30,47: LabelledConnectivity<2>); the third
             // column of the host table repeats the body and is not handed over
             std::vector<std::array<int32_t, 2>> c2;
             for (const auto& r : T.conn) c2.push_back({r[0], r[1]});
-            B.potential(KINDS[kind].name, c2);
+            pot = B.potential(KINDS[kind].name, c2);
         }
+        // constraint recording: every constraint is its own group; the kinds the hardening loop does not visit (springs, controllers) have no tolerance
+        stark.constraint_sources.push_back({pot, [this, kind]() {
+                                                const Table& tab = tables[kind];
+                                                return kind <= AngleLimits ? tab.tolerance : std::vector<double>(tab.conn.size(), std::numeric_limits<double>::max());
+                                            }});
     }
 }
 bool EnergyRigidBodyConstraints::_is_converged_state_valid()

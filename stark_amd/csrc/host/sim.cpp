@@ -58,6 +58,8 @@ void Stark::ensure_registered()
     budget_recorded = false;
     contacts_recorded = false;
     friction_recorded = false;
+    constraints_recorded = false;
+    constraint_sources.clear();
     contact_labels = nullptr;
     budget_inertia_sources.clear();
     budget_rigid_source = BudgetRigidSource{};
@@ -233,6 +235,20 @@ bool Stark::run_one_step()
             friction_time = current_time + dt;
             friction_recorded = true;
         }
+        if (constraint_recording) {
+            for (ConstraintRecorded& r : constraint_recorded) r = ConstraintRecorded{};
+            for (const ConstraintSource& src : constraint_sources) {
+                std::vector<double> tol = src.tolerance();
+                bool any_finite = false;
+                for (double t : tol) any_finite = any_finite || t < std::numeric_limits<double>::max();
+                int32_t kind = -1;
+                check(constraint_record(ctx, src.potential, any_finite ? tol.data() : nullptr, (int32_t)tol.size(), constraint_about.data(), &kind));
+                if (!any_finite) tol.clear();
+                constraint_recorded[(size_t)kind] = {true, std::move(tol)};
+            }
+            constraints_time = current_time + dt;
+            constraints_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -378,6 +394,31 @@ void Stark::get_contacts(ContactReport& out, bool sizes_only)
     out.pairs.resize(8 * (size_t)out.n_groups * out.n_groups);
     check(contact_report_fetch(ctx, out.rows_i.data(), out.rows_d.data(), &out.n_rows, out.vertices.data(), out.vertex_group.data(), out.vertex_source.data(), &out.n_vertices,
                                out.pairs.data(), &out.n_groups));
+}
+void Stark::record_constraints(bool enabled, const Vec3& about)
+{
+    constraint_recording = enabled;
+    constraint_about = about;
+    constraints_recorded = false;
+}
+void Stark::get_constraints(int kind, ConstraintKindReport& out, bool sizes_only)
+{
+    if (!constraint_recording) throw std::runtime_error("get_constraints: constraint recording is off (record_constraints)");
+    if (!ctx || !constraints_recorded) throw std::runtime_error("get_constraints: no time step has been accepted since recording was switched on");
+    if (kind < 0 || kind >= (int)constraint_recorded.size()) throw std::runtime_error("get_constraints: no kind " + std::to_string(kind));
+    out = ConstraintKindReport{};
+    out.time = constraints_time;
+    const ConstraintRecorded& r = constraint_recorded[(size_t)kind];
+    out.present = r.present;
+    if (!r.present) return;
+    out.tolerance = r.tolerance;
+    check(constraint_fetch(ctx, kind, nullptr, nullptr, nullptr, nullptr, &out.n_rows, &out.n_groups));
+    if (sizes_only) return;
+    out.rows.resize((size_t)16 * out.n_rows);
+    out.aux.resize((size_t)2 * out.n_rows);
+    out.ids.resize((size_t)4 * out.n_rows);
+    out.groups.resize((size_t)12 * out.n_groups);
+    check(constraint_fetch(ctx, kind, out.rows.data(), out.aux.data(), out.ids.data(), out.groups.data(), nullptr, nullptr));
 }
 void Stark::record_friction(bool enabled)
 {
@@ -686,7 +727,8 @@ void EnergyPrescribedPositions::register_potentials(mistark_ctx* ctx)
     B.add(stiffness.data(), (int64_t)stiffness.size(), 1, 2);
     id_stiffness = B.b.back().array;
     B.add_id(stark.dt_array(), 1, -1);
-    B.potential("EnergyPrescribedPositions", conn);
+    const int pot = B.potential("EnergyPrescribedPositions", conn);
+    stark.constraint_sources.push_back({pot, [this]() { return tolerance; }});
     targets_dirty = stiffness_dirty = false;
 }
 void EnergyPrescribedPositions::_before_energy_evaluation()

@@ -217,6 +217,30 @@ public:
     void record_friction(bool enabled);
     void get_friction(FrictionReport& out, bool sizes_only = false);  // sizes_only: counts, labels and time; nothing is downloaded
     bool friction_recording = false, friction_recorded = false;
+    // Constraint recording (off by default; not in the reference): at the same place, before on_time_step_accepted (the stiffness reported is the one
+    // the step was solved with), one constraint report (include/mistark.h "constraint report": row records, group records about `about`) per registered
+    // constraint potential, with the tolerances the host tables hold (a table whose tolerances are all numeric_limits<double>::max(): none), into a
+    // device set per kind; kept there until get_constraints() downloads one. Off: nothing is launched or allocated.
+    struct ConstraintKindReport
+    {
+        bool present = false;                   // a potential of the kind is registered
+        int64_t n_rows = 0;
+        int32_t n_groups = 0;
+        std::vector<double> rows, aux, groups;  // [n_rows][16], [n_rows][2], [n_groups][12]
+        std::vector<int32_t> ids;               // [n_rows][4]
+        std::vector<double> tolerance;          // [n_groups]; empty: none was passed
+        double time = 0.0;                      // simulation time of the accepted step
+    };
+    void record_constraints(bool enabled, const Vec3& about = {0.0, 0.0, 0.0});
+    void get_constraints(int kind, ConstraintKindReport& out, bool sizes_only = false);  // kind: 0..16, registry order of the seventeen
+    bool constraint_recording = false, constraints_recorded = false;
+    // what the constraint models note while they register: the potential and where its groups' tolerances are read when a step is recorded
+    struct ConstraintSource
+    {
+        int potential = -1;
+        std::function<std::vector<double>()> tolerance;  // one per group
+    };
+    std::vector<ConstraintSource> constraint_sources;
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -231,7 +255,14 @@ private:
     std::vector<std::string> force_groups;
     bool forces_recorded = false;  // ... in the current engine context
     Vec3 budget_about = {0.0, 0.0, 0.0};
-    double budget_time = 0.0, contacts_time = 0.0, friction_time = 0.0;
+    double budget_time = 0.0, contacts_time = 0.0, friction_time = 0.0, constraints_time = 0.0;
+    Vec3 constraint_about = {0.0, 0.0, 0.0};
+    struct ConstraintRecorded  // per kind code, as recorded at the last accepted step
+    {
+        bool present = false;
+        std::vector<double> tolerance;
+    };
+    std::array<ConstraintRecorded, 17> constraint_recorded{};
     std::vector<int32_t> budget_pots;       // the potentials of slot 0, as recorded
     std::vector<std::string> budget_names;  // ... and their names
     void _initialize();

@@ -875,6 +875,30 @@ int mistark_sim_get_friction(mistark_sim* s, int64_t* n_rows, int64_t* n_vertice
     if (labels) std::memcpy(labels, lb.c_str(), lb.size() + 1);
     SIM_END
 }
+int mistark_sim_record_constraints(mistark_sim* s, int enabled, const double about[3])
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_constraints(enabled != 0, about ? Vec3{about[0], about[1], about[2]} : Vec3{0.0, 0.0, 0.0});
+    SIM_END
+}
+int mistark_sim_get_constraints(mistark_sim* s, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, int32_t* has_tolerance, double* time, double* rows, double* aux,
+                                int32_t* ids, double* groups, double* tolerance)
+{
+    SIM_BEGIN
+    Stark::ConstraintKindReport r;
+    s->sim->get_stark().get_constraints(kind, r, !rows && !aux && !ids && !groups);  // (the size query downloads nothing)
+    if (present) *present = r.present ? 1 : 0;
+    if (n_rows) *n_rows = r.n_rows;
+    if (n_groups) *n_groups = r.n_groups;
+    if (has_tolerance) *has_tolerance = r.tolerance.empty() ? 0 : 1;
+    if (time) *time = r.time;
+    if (rows) std::copy(r.rows.begin(), r.rows.end(), rows);
+    if (aux) std::copy(r.aux.begin(), r.aux.end(), aux);
+    if (ids) std::copy(r.ids.begin(), r.ids.end(), ids);
+    if (groups) std::copy(r.groups.begin(), r.groups.end(), groups);
+    if (tolerance) std::copy(r.tolerance.begin(), r.tolerance.end(), tolerance);
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

@@ -424,6 +424,34 @@ class Engine:
                                              out.ctypes.data if out.size else None))
         return out
 
+    # ---- constraint report (include/mistark.h "constraint report") ---------------------------------------------------------
+    def constraint_report(self, pot: int, tolerance=None, n_groups=None) -> dict:
+        """The row records of a penalty-constraint potential (prescribed positions, attachments, rigid-body constraints) at the current DoFs, columns
+        named (constraint_rows_dict). tolerance: one per group, flags rows beyond it; n_groups defaults to its length."""
+        tol = None if tolerance is None else np.ascontiguousarray(tolerance, dtype=np.float64).reshape(-1)
+        ng = int(n_groups) if n_groups is not None else (0 if tol is None else tol.size)
+        if tol is not None and tol.size < ng:
+            raise ValueError("constraint_report: %d tolerances for %d groups" % (tol.size, ng))
+        tp = tol.ctypes.data if tol is not None and tol.size else None
+        n, kind = C.c_int64(), C.c_int32()
+        self._ck(self.L.mistark_potential_constraint_report(self.h, int(pot), tp, ng, None, None, None, C.byref(n), C.byref(kind)))
+        rec, aux, ids = np.zeros((n.value, 16)), np.zeros((n.value, 2)), np.zeros((n.value, 4), dtype=np.int32)
+        if n.value:
+            self._ck(self.L.mistark_potential_constraint_report(self.h, int(pot), tp, ng, rec.ctypes.data, aux.ctypes.data, ids.ctypes.data, C.byref(n), C.byref(kind)))
+        return constraint_rows_dict(rec, aux, ids, kind.value)
+
+    def constraint_group_report(self, pot: int, n_groups: int, tolerance=None, about=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """records [n_groups, 12] of a penalty-constraint potential: rows, active rows, rows beyond tolerance, largest |violation|, position in the
+        group's list of the first row attaining it (-1: none), resultant, moment about `about`, energy."""
+        tol = None if tolerance is None else np.ascontiguousarray(tolerance, dtype=np.float64).reshape(-1)
+        if tol is not None and tol.size < int(n_groups):
+            raise ValueError("constraint_group_report: %d tolerances for %d groups" % (tol.size, int(n_groups)))
+        ab = np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        out = np.zeros((int(n_groups), 12))
+        self._ck(self.L.mistark_constraint_group_report(self.h, int(pot), tol.ctypes.data if tol is not None and tol.size else None, int(n_groups), ab.ctypes.data,
+                                                        out.ctypes.data if out.size else None))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)
@@ -514,6 +542,22 @@ def contact_rows_dict(ri, rd):
     return dict(ints=ri, doubles=rd, bounds=bounds, table=ri[:, 0], source=ri[:, 1], type=ri[:, 2], group_a=ri[:, 3], group_b=ri[:, 4], prim_a=ri[:, 5], prim_b=ri[:, 6],
                 flags=ri[:, 7], d=rd[:, 0], dhat=rd[:, 1], point_a=rd[:, 2:5], point_b=rd[:, 5:8], normal=rd[:, 8:11], mollifier=rd[:, 11], fn=rd[:, 12], E=rd[:, 13],
                 params=rd[:, 14:16])
+
+
+CONSTRAINT_KINDS = ("EnergyPrescribedPositions", "rb_constraint_global_points", "rb_constraint_global_directions", "rb_constraint_points", "rb_constraint_point_on_axis",
+                    "rb_constraint_distances", "rb_constraint_distance_limits", "rb_constraint_directions", "rb_constraint_angle_limits", "rb_constraint_damped_spring",
+                    "rb_constraint_linear_velocity", "rb_constraint_angular_velocity", "EnergyAttachments_d_d_p_p", "EnergyAttachments_d_d_p_e", "EnergyAttachments_d_d_p_t",
+                    "EnergyAttachments_d_d_e_e", "EnergyAttachments_rb_d")
+CONSTRAINT_UNITS = ("m", "m", "deg", "m", "m", "m", "m", "deg", "deg", "m", "m/s", "deg/s", "m", "m", "m", "m", "m")
+
+
+def constraint_rows_dict(rec, aux, ids, kind):
+    """The row arrays of a constraint report with their columns named (views; flags as integers)."""
+    flags = rec[:, 15].astype(np.int64)
+    return dict(records=rec, aux=aux, ids=ids, kind=int(kind), name=CONSTRAINT_KINDS[kind] if 0 <= kind < 17 else None, unit=CONSTRAINT_UNITS[kind] if 0 <= kind < 17 else None,
+                violation=rec[:, 0], reaction=rec[:, 1], force=rec[:, 2:5], torque=rec[:, 5:8], anchor_a=rec[:, 8:11], anchor_b=rec[:, 11:14], E=rec[:, 14], flags=flags,
+                active=(flags & 1) != 0, beyond_tolerance=(flags & 2) != 0, out_of_range=(flags & 4) != 0, damper_velocity=aux[:, 0], damper_force=aux[:, 1],
+                group=ids[:, 0], row_a=ids[:, 2], row_b=ids[:, 3])
 
 
 def contact_vertices_dict(rec, group, source_index):

@@ -143,6 +143,8 @@ def _lib():
         L.mistark_sim_get_budget.argtypes = [p, I32, I32, I64, I64, D, p, p, p, p, p]
         L.mistark_sim_record_contacts.argtypes = [p, C.c_int]
         L.mistark_sim_get_contacts.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
+        L.mistark_sim_record_constraints.argtypes = [p, C.c_int, D]
+        L.mistark_sim_get_constraints.argtypes = [p, C.c_int, I32, I64, I32, I32, D, p, p, p, p, p]
         L.mistark_sim_record_friction.argtypes = [p, C.c_int]
         L.mistark_sim_get_friction.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
         _bound = True
@@ -569,6 +571,32 @@ class Simulation:
                      angular_momentum=sum((o["angular_momentum"] for o in objects), np.zeros(3)), kinetic=sum(o["kinetic"] for o in objects),
                      gravitational=sum(o["gravitational"] for o in objects))
         return dict(potentials=potentials, objects=objects, total=total, time=t.value)
+
+    # ---- constraint recording ----------------------------------------------------------------------------------------------
+    def record_constraints(self, on=True, about=(0.0, 0.0, 0.0)):
+        """Every accepted step then keeps the constraint report of the state it converged at (row and group records of every registered prescribed-position,
+        attachment and rigid-body constraint potential, with the tolerances the scene holds) on the device; group moments about `about`."""
+        ab = (C.c_double * 3)(*[float(v) for v in about])
+        self._ck(self.L.mistark_sim_record_constraints(self.h, int(bool(on)), ab))
+
+    def constraints(self):
+        """The constraint report of the last accepted step: dict(kinds={registry name: dict(rows=Engine.constraint_report()'s dict, groups [n_groups, 12],
+        tolerance [n_groups] (inf where the scene holds none), unit)}, time); kinds without rows are left out. Raises while recording is off."""
+        from .engine import CONSTRAINT_KINDS, CONSTRAINT_UNITS, constraint_rows_dict
+        kinds, time = {}, 0.0
+        ptr = lambda a: a.ctypes.data if a.size else None
+        for kind, name in enumerate(CONSTRAINT_KINDS):
+            pres, n, g, ht, t = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int32(), C.c_double()
+            self._ck(self.L.mistark_sim_get_constraints(self.h, kind, C.byref(pres), C.byref(n), C.byref(g), C.byref(ht), C.byref(t), None, None, None, None, None))
+            time = t.value
+            if not pres.value or n.value == 0:
+                continue
+            rec, aux, ids = np.zeros((n.value, 16)), np.zeros((n.value, 2)), np.zeros((n.value, 4), dtype=np.int32)
+            groups, tol = np.zeros((g.value, 12)), np.zeros(g.value)
+            self._ck(self.L.mistark_sim_get_constraints(self.h, kind, C.byref(pres), C.byref(n), C.byref(g), C.byref(ht), C.byref(t), ptr(rec), ptr(aux), ptr(ids), ptr(groups),
+                                                        ptr(tol) if ht.value else None))
+            kinds[name] = dict(rows=constraint_rows_dict(rec, aux, ids, kind), groups=groups, tolerance=tol if ht.value else np.full(g.value, np.inf), unit=CONSTRAINT_UNITS[kind])
+        return dict(kinds=kinds, time=time)
 
     # ---- contact recording -------------------------------------------------------------------------------------------------
     def record_contacts(self, on=True):
