@@ -235,6 +235,44 @@ int mistark_potential_constraint_report(mistark_ctx* ctx, int potential, const d
 /* out[g][12], g < n_groups; a declared group without rows reports zeros with -1 in slot 4. */
 int mistark_constraint_group_report(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, const double about[3], double* out);
 
+/* ---- bending report ---------------------------------------------------------------------------------------------------------
+ * Where a sheet creases, how sharply it curves, what moment its hinges carry and how much energy bending holds: the two cloth bending potentials,
+ * EnergyDiscreteShells (kind 0, "complete") and EnergyBendingFlat (kind 1, "flat"), at the current DoFs (x1 = x0 + dt v1). A pipeline of its own beside
+ * mistark_eval, like the readouts above: it writes only buffers of its own, uses no floating-point atomics and launches nothing unless it is called; two
+ * reports of one state give the same bits. Refused, with the cause in the message: sharded contexts (single-rank accessor), registration-only contexts, any
+ * other potential (by name), user-defined potentials, bad or duplicate ids, n_groups not larger than the largest group id of the table, a negative or
+ * non-finite threshold. The group of a row is the connectivity entry it reads its stiffness with (column 1 of the tables the host mirror registers; group 0
+ * for a potential bound to one global stiffness). Local nodes 0 and 1 of a row are the hinge edge, 2 and 3 the opposite vertices.
+ * Row record, 16 doubles, the same for both kinds:
+ *   0 theta1: the angle as the potential's own dihedral_angle() computes it, acos((1 - 1e-12) n0.n1): in [1.41e-6, pi], blind to the fold direction
+ *   1 phi1: signed fold angle atan2(e0 . (n0 x n1), n0 . n1) of the unit vectors, well conditioned near flat; its sign is the fold direction
+ *   2 rest angle (complete: the bound rest angle; flat: 0) | 3 angle rate (theta1 - theta0) / dt, theta0 the same function at x0
+ *   4 current hinge length | 5 rest hinge area a = (A0 + A1) / 3 from the potential's own data (complete scale^2 rest_len rest_height; flat 1 / (2 coef))
+ *   6 normal curvature across the hinge kappa (complete theta1 / (3 scale rest_height); flat |s| / (3 a), s = sum K_i x1_i; both tend to 1 / R on a mesh
+ *     inscribed in a cylinder of radius R) | 7 rest curvature (complete rest / (3 scale rest_height); flat 0)
+ *   8 bending moment [J/rad]: complete dE/dtheta1 = ratio (2 k (theta1 - rest) + (damping / dt) (theta1 - theta0)); flat k coef |s| l1 cos(theta1 / 2),
+ *     which is dE/dtheta for a fold that leaves both triangles rigid: k l sin(theta) / (2 h_e), for one stiffness a quarter of the complete model's
+ *     2 k theta l / h_e at small angles
+ *   9 elastic energy (complete k (theta1 - rest)^2 ratio; flat the whole element energy) | 10 damping energy (complete: the potential's damping term;
+ *     flat 0); 9 + 10 is the element energy mistark_eval computes
+ *   11..13 unit hinge normal (n0 + n1) / |n0 + n1| (zeros for a hinge folded onto itself) | 14 group | 15 flags: +1 degenerate, +2 |theta1 - rest| beyond
+ *     the threshold of the row's group
+ *   A hinge is degenerate when a triangle of its stencil has zero area at x1 or the hinge has zero length: flag 1 (never flag 2), and zeros in every field
+ *   that needs a normal: 0, 1, 3, 8, 11..13, and for the complete kind 6, 9 and 10. Finite inputs give finite records.
+ * Nodal record, 6 doubles per block row: only the two edge endpoints of a hinge contribute, each with weight a / 2.
+ *   0 weighted mean kappa | 1 weighted mean kappa - kappa_rest | 2 energy share, sum of (9 + 10) / 2 (the nodal sum is the total) | 3 largest
+ *   |theta1 - rest| | 4 hinges ending at the node | 5 weight sum. Rows no hinge ends at are six zeros.
+ * Group record, 10 doubles: 0 hinges | 1 degenerate hinges | 2 hinges beyond threshold | 3 largest |theta1 - rest| | 4 position in the group's list (table
+ *   order) of the first row attaining it, -1 for a group without rows | 5 sum of 9 | 6 sum of 10 | 7 sum of a | 8 sum of a (kappa - kappa_rest)^2 |
+ *   9 a-weighted mean |kappa - kappa_rest| */
+/* threshold: [n_groups] in rad, or NULL (then n_groups may be 0 and no row is flagged). out: [row][16] or NULL (n_rows and kind alone: a size query,
+ * nothing is launched). An empty table launches nothing and reports zero rows. */
+int mistark_potential_bending_report(mistark_ctx* ctx, int potential, const double* threshold, int32_t n_groups, double* out, int64_t* n_rows, int32_t* kind);
+/* out_host[block row][6] over the listed potentials; both kinds may be listed together (their units agree). */
+int mistark_nodal_bending(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out_host);
+/* out[g][10], g < n_groups; a declared group without rows reports zeros with -1 in slot 4. */
+int mistark_bending_group_report(mistark_ctx* ctx, int potential, const double* threshold, int32_t n_groups, double* out);
+
 /* ---- projection + assembly ------------------------------------------------------------------------------------------ */
 /* ElementHessians::project_to_PD_inplace__all / project_to_PD_for_update__selectively (ElementHessians.cpp:48-67,79-182;
  * project_to_PD.cpp:12-32). active_blocks: NULL = all elements, else ndofs/3 flags; only not-yet-projected elements
@@ -451,7 +489,8 @@ int mistark_sync(mistark_ctx* ctx);
  * launched, chunks of the element list the last inertia budget was summed in), "contact_reports" / "contact_report_long_rows" (contact report calls
  * that launched, mistark_contact.h; collision vertices of the last report summed by a whole wavefront), "friction_reports" / "friction_report_long_rows"
  * (the same two for the friction report), "constraint_reports" / "constraint_report_chunks" (constraint report calls that launched, chunks the last group
- * report was summed in). */
+ * report was summed in), "bending_reports" / "bending_report_long_rows" / "bending_report_chunks" (bending report calls that launched, block rows of the
+ * last nodal stage summed by a whole wavefront, chunks the last group stage was summed in). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

@@ -259,6 +259,17 @@ int mistark_sim_record_constraints(mistark_sim* sim, int enabled, const double a
  * rows [n_rows x 16], aux [n_rows x 2], ids [n_rows x 4], groups [n_groups x 12], tolerance [n_groups] (written when has_tolerance is 1). */
 int mistark_sim_get_constraints(mistark_sim* sim, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, int32_t* has_tolerance, double* time, double* rows,
                                 double* aux, int32_t* ids, double* groups, double* tolerance);
+/* Bending recording (off by default; not in the reference), at the same place inside the step: one bending report (mistark.h "bending report": row records
+ * of 16 doubles, nodal records of 6, group records of 10) of the cloth bending potentials the scene registers, EnergyDiscreteShells (kind 0) and
+ * EnergyBendingFlat (kind 1), the nodal records over both. threshold_rad flags the hinges whose |theta1 - rest| exceeds it, in every group (0: none;
+ * negative or not finite: refused). Results stay on the device until they are asked for. With recording off nothing is launched or allocated. */
+int mistark_sim_record_bending(mistark_sim* sim, int enabled, double threshold_rad);
+/* The report of one kind at the last accepted step. Every output is nullable; a first call with the buffers NULL gives the sizes and downloads nothing.
+ * present: 0 when the scene registers no potential of the kind (everything else is then 0). rows [n_rows x 16], groups [n_groups x 10]: one group per
+ * cloth the scene added, in that order. */
+int mistark_sim_get_bending(mistark_sim* sim, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, double* time, double* rows, double* groups);
+/* points_out [n_points x 6]: the nodal records of both kinds together. */
+int mistark_sim_get_nodal_bending(mistark_sim* sim, double* points_out);
 /* Contact recording (off by default; not in the reference), at the same place inside the step: one contact report of the end-of-step state
  * (mistark_contact.h "contact report": the rows of the installed barrier tables, the vertex records, the group-pair records), after the Newton callbacks
  * that precede an evaluation, so that the installed tables are that state's. Results stay on the device until they are asked for. With recording off

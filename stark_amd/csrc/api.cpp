@@ -586,6 +586,9 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "budget_chunks") *out = c.n_budget_chunks;
     else if (n == "constraint_reports") *out = c.n_constraint_reports;
     else if (n == "constraint_report_chunks") *out = c.n_constraint_chunks;
+    else if (n == "bending_reports") *out = c.n_bending_reports;
+    else if (n == "bending_report_long_rows") *out = bending_long_rows(c);
+    else if (n == "bending_report_chunks") *out = c.n_bending_chunks;
     else if (n == "contact_reports") *out = c.n_contact_reports;
     else if (n == "contact_report_long_rows") *out = contact_report_long_rows(c);
     else if (n == "friction_reports") *out = c.n_friction_reports;
@@ -755,6 +758,26 @@ int mistark_constraint_group_report(mistark_ctx* ctx, int potential, const doubl
 {
     API_BEGIN
     constraint_groups_host(ctx->c, potential, tolerance, n_groups, about, out);
+    API_END(0)
+}
+
+// ---- bending report (bending_report.hip) -----------------------------------------------------------------------------------
+int mistark_potential_bending_report(mistark_ctx* ctx, int potential, const double* threshold, int32_t n_groups, double* out, int64_t* n_rows, int32_t* kind)
+{
+    API_BEGIN
+    bending_rows_host(ctx->c, potential, threshold, n_groups, out, n_rows, kind);
+    API_END(0)
+}
+int mistark_nodal_bending(mistark_ctx* ctx, const int32_t* potentials, int32_t n, double* out_host)
+{
+    API_BEGIN
+    bending_nodal_host(ctx->c, potentials, n, out_host);
+    API_END(0)
+}
+int mistark_bending_group_report(mistark_ctx* ctx, int potential, const double* threshold, int32_t n_groups, double* out)
+{
+    API_BEGIN
+    bending_groups_host(ctx->c, potential, threshold, n_groups, out);
     API_END(0)
 }
 
@@ -1562,6 +1585,24 @@ int constraint_fetch(mistark_ctx* ctx, int kind, double* out, double* aux, int32
 {
     API_BEGIN
     constraint_fetch_kind(ctx->c, kind, out, aux, ids, groups, n_rows, n_groups);
+    API_END(0)
+}
+int bending_record(mistark_ctx* ctx, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups)
+{
+    API_BEGIN
+    bending_record_step(ctx->c, pot_complete, pot_flat, threshold, n_groups);
+    API_END(0)
+}
+int bending_fetch(mistark_ctx* ctx, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups)
+{
+    API_BEGIN
+    bending_fetch_kind(ctx->c, kind, rows, groups, n_rows, n_groups);
+    API_END(0)
+}
+int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows)
+{
+    API_BEGIN
+    mistark::bending_fetch_nodal(ctx->c, out, n_rows);
     API_END(0)
 }
 int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n)

@@ -654,6 +654,37 @@ struct Context
     int64_t n_constraint_reports = 0;  // counter "constraint_reports": calls that launched
     int64_t n_constraint_chunks = 0;   // counter "constraint_report_chunks": chunks of the last group report
 
+    // Bending report (bending_report.hip): the seventh pipeline beside eval(). Row records of the cloth bending potentials at the current DoFs, field-major
+    // ([16][rows of the selection]); contributions (row, edge endpoint) sorted by block row, one ordered sum per row -> bdr_out [nbr][6]; the rows listed
+    // per group (stable) and cut into chunks of BEND_CHUNK rows, one workgroup per chunk -> bdr_partial [chunk][10], one workgroup per group folds its
+    // chunks -> bdr_groups [group][10]. Nothing but these buffers is written.
+    DevBuf<double> bdr_rec, bdr_out, bdr_groups, bdr_thr, bdr_partial;
+    DevBuf<uint32_t> bdr_key, bdr_key_alt, bdr_val, bdr_val_alt;
+    DevBuf<uint32_t> bdr_stat;         // [0]: rows of the last nodal stage summed by a whole wavefront (counter "bending_report_long_rows")
+    DevBuf<unsigned char> bdr_desc;
+    DevBuf<uint8_t> bdr_cub_tmp;
+    struct BendingPlan                 // per potential: its rows group by group and the chunk table (per chunk: first item, item count; then per group (+1): first chunk)
+    {
+        DevBuf<uint32_t> items;
+        DevBuf<int32_t> chunks;
+        uint64_t conn_version = 0;
+        int n_elem = -1, n_groups = -1;
+        int64_t n_chunks = 0;
+    };
+    std::map<int, BendingPlan> bdr_plans;
+    struct BendingSlot                 // what the host mirror records inside a time step and keeps on the device; kind 0 complete, 1 flat
+    {
+        DevBuf<double> rec, nodal, groups[2];
+        int64_t N = -1;                // columns of rec: the rows of both kinds (-1: nothing yet)
+        int64_t n_rows[2] = {0, 0}, col0[2] = {0, 0};
+        int32_t n_groups = 0;
+        int64_t nbr = 0;
+    };
+    BendingSlot bdr_slot;
+    int64_t n_bending_reports = 0;     // counter "bending_reports": calls that launched
+    int64_t n_bending_chunks = 0;      // counter "bending_report_chunks": chunks of the last group stage
+    bool bdr_stat_valid = false;
+
     int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -826,6 +857,14 @@ void constraint_rows_host(Context& c, int pot, const double* tolerance, int32_t 
 void constraint_groups_host(Context& c, int pot, const double* tolerance, int32_t n_groups, const double* about, double* out);
 void constraint_record_kind(Context& c, int pot, const double* tolerance, int32_t n_groups, const double* about, int32_t* kind);
 void constraint_fetch_kind(Context& c, int kind, double* out, double* aux, int32_t* ids, double* groups, int64_t* n_rows, int32_t* n_groups);
+// Bending report (bending_report.hip, records as bending_report.hpp lays them out). kind: 0 complete (EnergyDiscreteShells), 1 flat (EnergyBendingFlat).
+void bending_rows_host(Context& c, int pot, const double* threshold, int32_t n_groups, double* out, int64_t* n_rows, int32_t* kind);
+void bending_nodal_host(Context& c, const int32_t* pots, int32_t n, double* out_host);
+void bending_groups_host(Context& c, int pot, const double* threshold, int32_t n_groups, double* out);
+int64_t bending_long_rows(Context& c);  // counter "bending_report_long_rows"
+void bending_record_step(Context& c, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups);  // into Context::bdr_slot; -1: not registered
+void bending_fetch_kind(Context& c, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups);
+void bending_fetch_nodal(Context& c, double* out, int64_t n_rows);
 int find_kind(const char* name);
 int kind_nb(int kind);
 int kind_nbind(int kind);

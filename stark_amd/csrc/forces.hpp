@@ -31,6 +31,11 @@ int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n);
 // constraint report (constraint_report.hip): rows and groups of one potential into the set of its kind (0..16), kept on the device until fetched
 int constraint_record(mistark_ctx* ctx, int potential, const double* tolerance, int32_t n_groups, const double about[3], int32_t* kind);
 int constraint_fetch(mistark_ctx* ctx, int kind, double* out, double* aux, int32_t* ids, double* groups, int64_t* n_rows, int32_t* n_groups);
+// bending report (bending_report.hip): rows, nodal records and groups of the registered bending potentials (-1: not registered) into the device set of the
+// host mirror; kind 0 complete, 1 flat; nodal out[n_rows][6], n_rows = block rows of the DoF vector
+int bending_record(mistark_ctx* ctx, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups);
+int bending_fetch(mistark_ctx* ctx, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups);
+int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows);
 // contact report (contact_report.hip) of the current state into the device set of the host mirror; its three parts (null outputs are skipped, the counts
 // always come back)
 int contact_report_record(mistark_ctx* ctx);

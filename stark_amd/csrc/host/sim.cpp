@@ -60,6 +60,8 @@ void Stark::ensure_registered()
     friction_recorded = false;
     constraints_recorded = false;
     constraint_sources.clear();
+    bending_recorded = false;
+    bending_source = BendingSource{};
     contact_labels = nullptr;
     budget_inertia_sources.clear();
     budget_rigid_source = BudgetRigidSource{};
@@ -249,6 +251,14 @@ bool Stark::run_one_step()
             constraints_time = current_time + dt;
             constraints_recorded = true;
         }
+        if (bending_recording) {
+            const BendingSource& src = bending_source;
+            const std::vector<double> thr((size_t)src.n_groups, bending_threshold);
+            check(bending_record(ctx, src.pot_complete, src.pot_flat, bending_threshold > 0.0 && src.n_groups > 0 ? thr.data() : nullptr, src.n_groups));
+            bending_recorded_source = src;
+            bending_time = current_time + dt;
+            bending_recorded = true;
+        }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
         current_time += dt;
@@ -419,6 +429,40 @@ void Stark::get_constraints(int kind, ConstraintKindReport& out, bool sizes_only
     out.ids.resize((size_t)4 * out.n_rows);
     out.groups.resize((size_t)12 * out.n_groups);
     check(constraint_fetch(ctx, kind, out.rows.data(), out.aux.data(), out.ids.data(), out.groups.data(), nullptr, nullptr));
+}
+void Stark::record_bending(bool enabled, double threshold_rad)
+{
+    if (!(threshold_rad >= 0.0) || !std::isfinite(threshold_rad)) throw std::runtime_error("record_bending: the threshold is negative or not finite");
+    bending_recording = enabled;
+    bending_threshold = threshold_rad;
+    bending_recorded = false;
+}
+void Stark::get_bending(int kind, BendingKindReport& out, bool sizes_only)
+{
+    if (!bending_recording) throw std::runtime_error("get_bending: bending recording is off (record_bending)");
+    if (!ctx || !bending_recorded) throw std::runtime_error("get_bending: no time step has been accepted since recording was switched on");
+    if (kind < 0 || kind > 1) throw std::runtime_error("get_bending: no kind " + std::to_string(kind));
+    out = BendingKindReport{};
+    out.time = bending_time;
+    out.present = (kind == 0 ? bending_recorded_source.pot_complete : bending_recorded_source.pot_flat) >= 0;
+    if (!out.present) return;
+    check(bending_fetch(ctx, kind, nullptr, nullptr, &out.n_rows, &out.n_groups));
+    if (sizes_only) return;
+    out.rows.resize((size_t)16 * out.n_rows);
+    out.groups.resize((size_t)10 * out.n_groups);
+    check(bending_fetch(ctx, kind, out.rows.data(), out.groups.data(), nullptr, nullptr));
+}
+void Stark::get_nodal_bending(double* points_out)
+{
+    if (!bending_recording) throw std::runtime_error("get_nodal_bending: bending recording is off (record_bending)");
+    if (!ctx || !bending_recorded) throw std::runtime_error("get_nodal_bending: no time step has been accepted since recording was switched on");
+    if (!points_out || force_n_points <= 0) return;
+    const int64_t nbr = mistark_ndofs(ctx) / 3;
+    std::vector<double> all((size_t)nbr * 6);
+    check(bending_fetch_nodal(ctx, all.data(), nbr));
+    const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
+    if (r0 < 0) throw std::runtime_error("get_nodal_bending: the point set has no DoFs");
+    std::copy(all.begin() + 6 * r0, all.begin() + 6 * (r0 + force_n_points), points_out);
 }
 void Stark::record_friction(bool enabled)
 {
@@ -997,7 +1041,7 @@ void EnergyDiscreteShells::register_potentials(mistark_ctx* ctx)
         B.add(bending_stiffness.data(), ng, 1, 1);
         B.add(bending_damping.data(), ng, 1, 1);
         B.add_id(stark.dt_array(), 1, -1);
-        B.potential("EnergyDiscreteShells", conn_complete);
+        stark.bending_source.pot_complete = B.potential("EnergyDiscreteShells", conn_complete);
     }
     if (!conn_flat_rest.empty()) {
         // EnergyDiscreteShells.cpp:71-76
@@ -1008,8 +1052,9 @@ void EnergyDiscreteShells::register_potentials(mistark_ctx* ctx)
         B.add(bergou_coef.data(), (int64_t)bergou_coef.size(), 1, 0);
         B.add(bending_stiffness.data(), ng, 1, 1);
         B.add_id(stark.dt_array(), 1, -1);
-        B.potential("EnergyBendingFlat", conn_flat_rest);
+        stark.bending_source.pot_flat = B.potential("EnergyBendingFlat", conn_flat_rest);
     }
+    stark.bending_source.n_groups = (int32_t)ng;
 }
 EnergyDiscreteShells::Handler EnergyDiscreteShells::add(const PointSetHandler& set, const std::vector<std::array<int, 3>>& tris, const Params& p)
 {

@@ -241,6 +241,30 @@ public:
         std::function<std::vector<double>()> tolerance;  // one per group
     };
     std::vector<ConstraintSource> constraint_sources;
+    // Bending recording (off by default; not in the reference): at the same place, one bending report (include/mistark.h "bending report": row records,
+    // nodal records, group records) of the two cloth bending potentials the scene registers, into one device set; kept there until get_bending() /
+    // get_nodal_bending() download it. threshold_rad: flags hinges whose |theta1 - rest| exceeds it, in every group (0: none). Off: nothing is launched
+    // or allocated.
+    struct BendingKindReport
+    {
+        bool present = false;       // the potential of the kind is registered
+        int64_t n_rows = 0;
+        int32_t n_groups = 0;
+        std::vector<double> rows;   // [n_rows][16]
+        std::vector<double> groups; // [n_groups][10]
+        double time = 0.0;          // simulation time of the accepted step
+    };
+    void record_bending(bool enabled, double threshold_rad = 0.0);
+    void get_bending(int kind, BendingKindReport& out, bool sizes_only = false);  // kind: 0 complete (EnergyDiscreteShells), 1 flat (EnergyBendingFlat)
+    void get_nodal_bending(double* points_out /* n_points x 6 */);
+    bool bending_recording = false, bending_recorded = false;
+    // what EnergyDiscreteShells notes while it registers: its two potentials (-1: none) and the number of its groups
+    struct BendingSource
+    {
+        int pot_complete = -1, pot_flat = -1;
+        int32_t n_groups = 0;
+    };
+    BendingSource bending_source;
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -257,6 +281,8 @@ private:
     Vec3 budget_about = {0.0, 0.0, 0.0};
     double budget_time = 0.0, contacts_time = 0.0, friction_time = 0.0, constraints_time = 0.0;
     Vec3 constraint_about = {0.0, 0.0, 0.0};
+    double bending_threshold = 0.0, bending_time = 0.0;
+    BendingSource bending_recorded_source;  // ... as recorded at the last accepted step
     struct ConstraintRecorded  // per kind code, as recorded at the last accepted step
     {
         bool present = false;

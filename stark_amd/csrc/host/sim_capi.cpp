@@ -899,6 +899,31 @@ int mistark_sim_get_constraints(mistark_sim* s, int kind, int32_t* present, int6
     if (tolerance) std::copy(r.tolerance.begin(), r.tolerance.end(), tolerance);
     SIM_END
 }
+int mistark_sim_record_bending(mistark_sim* s, int enabled, double threshold_rad)
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_bending(enabled != 0, threshold_rad);
+    SIM_END
+}
+int mistark_sim_get_bending(mistark_sim* s, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, double* time, double* rows, double* groups)
+{
+    SIM_BEGIN
+    Stark::BendingKindReport r;
+    s->sim->get_stark().get_bending(kind, r, !rows && !groups);  // (the size query downloads nothing)
+    if (present) *present = r.present ? 1 : 0;
+    if (n_rows) *n_rows = r.n_rows;
+    if (n_groups) *n_groups = r.n_groups;
+    if (time) *time = r.time;
+    if (rows) std::copy(r.rows.begin(), r.rows.end(), rows);
+    if (groups) std::copy(r.groups.begin(), r.groups.end(), groups);
+    SIM_END
+}
+int mistark_sim_get_nodal_bending(mistark_sim* s, double* points_out)
+{
+    SIM_BEGIN
+    s->sim->get_stark().get_nodal_bending(points_out);
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

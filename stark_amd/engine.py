@@ -452,6 +452,42 @@ class Engine:
                                                         out.ctypes.data if out.size else None))
         return out
 
+    # ---- bending report (include/mistark.h "bending report") ---------------------------------------------------------------
+    @staticmethod
+    def _thresholds(threshold, n_groups, who):
+        thr = None if threshold is None else np.ascontiguousarray(threshold, dtype=np.float64).reshape(-1)
+        ng = int(n_groups) if n_groups is not None else (0 if thr is None else thr.size)
+        if thr is not None and thr.size < ng:
+            raise ValueError("%s: %d thresholds for %d groups" % (who, thr.size, ng))
+        return thr, ng, (thr.ctypes.data if thr is not None and thr.size else None)
+
+    def bending_report(self, pot: int, threshold=None, n_groups=None) -> dict:
+        """The row records of a cloth bending potential (EnergyDiscreteShells: kind 0, EnergyBendingFlat: kind 1) at the current DoFs, columns named
+        (bending_rows_dict). threshold: one per group in rad, flags hinges whose |theta1 - rest| exceeds it; n_groups defaults to its length."""
+        thr, ng, tp = self._thresholds(threshold, n_groups, "bending_report")
+        n, kind = C.c_int64(), C.c_int32()
+        self._ck(self.L.mistark_potential_bending_report(self.h, int(pot), tp, ng, None, C.byref(n), C.byref(kind)))
+        rec = np.zeros((n.value, 16))
+        if n.value:
+            self._ck(self.L.mistark_potential_bending_report(self.h, int(pot), tp, ng, rec.ctypes.data, C.byref(n), C.byref(kind)))
+        return bending_rows_dict(rec, kind.value)
+
+    def nodal_bending(self, pots) -> np.ndarray:
+        """out[block rows, 6] over the listed bending potentials (both kinds may be listed together): area-weighted mean kappa, mean kappa - kappa_rest,
+        energy share, largest |theta1 - rest|, hinges ending at the node, weight sum."""
+        ids, ptr = self._pot_list(pots)
+        out = np.zeros((self.ndofs // 3, 6))
+        self._ck(self.L.mistark_nodal_bending(self.h, ptr, ids.size, out.ctypes.data))
+        return out
+
+    def bending_group_report(self, pot: int, n_groups: int, threshold=None) -> np.ndarray:
+        """records [n_groups, 10] of a cloth bending potential: hinges, degenerate, beyond threshold, largest |theta1 - rest|, position in the group's list
+        of the first row attaining it (-1: none), elastic energy, damping energy, area, sum a (kappa - kappa_rest)^2, area-weighted mean |kappa - kappa_rest|."""
+        thr, ng, tp = self._thresholds(threshold, n_groups, "bending_group_report")
+        out = np.zeros((ng, 10))
+        self._ck(self.L.mistark_bending_group_report(self.h, int(pot), tp, ng, out.ctypes.data if out.size else None))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)
@@ -558,6 +594,17 @@ def constraint_rows_dict(rec, aux, ids, kind):
                 violation=rec[:, 0], reaction=rec[:, 1], force=rec[:, 2:5], torque=rec[:, 5:8], anchor_a=rec[:, 8:11], anchor_b=rec[:, 11:14], E=rec[:, 14], flags=flags,
                 active=(flags & 1) != 0, beyond_tolerance=(flags & 2) != 0, out_of_range=(flags & 4) != 0, damper_velocity=aux[:, 0], damper_force=aux[:, 1],
                 group=ids[:, 0], row_a=ids[:, 2], row_b=ids[:, 3])
+
+
+BENDING_KINDS = ("EnergyDiscreteShells", "EnergyBendingFlat")
+
+
+def bending_rows_dict(rec, kind):
+    """The row array of a bending report with its columns named (views; flags and group as integers)."""
+    flags = rec[:, 15].astype(np.int64)
+    return dict(records=rec, kind=int(kind), name=BENDING_KINDS[kind] if 0 <= kind < 2 else None, theta=rec[:, 0], phi=rec[:, 1], rest_angle=rec[:, 2], rate=rec[:, 3],
+                length=rec[:, 4], area=rec[:, 5], kappa=rec[:, 6], kappa_rest=rec[:, 7], moment=rec[:, 8], E_elastic=rec[:, 9], E_damping=rec[:, 10], normal=rec[:, 11:14],
+                group=rec[:, 14].astype(np.int64), flags=flags, degenerate=(flags & 1) != 0, beyond_threshold=(flags & 2) != 0)
 
 
 def contact_vertices_dict(rec, group, source_index):

@@ -145,6 +145,9 @@ def _lib():
         L.mistark_sim_get_contacts.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
         L.mistark_sim_record_constraints.argtypes = [p, C.c_int, D]
         L.mistark_sim_get_constraints.argtypes = [p, C.c_int, I32, I64, I32, I32, D, p, p, p, p, p]
+        L.mistark_sim_record_bending.argtypes = [p, C.c_int, C.c_double]
+        L.mistark_sim_get_bending.argtypes = [p, C.c_int, I32, I64, I32, D, p, p]
+        L.mistark_sim_get_nodal_bending.argtypes = [p, p]
         L.mistark_sim_record_friction.argtypes = [p, C.c_int]
         L.mistark_sim_get_friction.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
         _bound = True
@@ -597,6 +600,33 @@ class Simulation:
                                                         ptr(tol) if ht.value else None))
             kinds[name] = dict(rows=constraint_rows_dict(rec, aux, ids, kind), groups=groups, tolerance=tol if ht.value else np.full(g.value, np.inf), unit=CONSTRAINT_UNITS[kind])
         return dict(kinds=kinds, time=time)
+
+    # ---- bending recording ---------------------------------------------------------------------------------------------------
+    def record_bending(self, on=True, threshold_rad=0.0):
+        """Every accepted step then keeps the bending report of the state it converged at (row, nodal and group records of the cloth bending potentials
+        the scene registers) on the device; threshold_rad flags hinges whose |theta1 - rest| exceeds it (0: none)."""
+        self._ck(self.L.mistark_sim_record_bending(self.h, int(bool(on)), float(threshold_rad)))
+
+    def bending(self):
+        """The bending report of the last accepted step: dict(kinds={registry name: dict(rows=Engine.bending_report()'s dict, groups [n_groups, 10])},
+        nodal [n_points, 6] over both kinds, time); kinds the scene does not register are left out. Raises while recording is off."""
+        from .engine import BENDING_KINDS, bending_rows_dict
+        kinds, time = {}, 0.0
+        ptr = lambda a: a.ctypes.data if a.size else None
+        for kind, name in enumerate(BENDING_KINDS):
+            pres, n, g, t = C.c_int32(), C.c_int64(), C.c_int32(), C.c_double()
+            self._ck(self.L.mistark_sim_get_bending(self.h, kind, C.byref(pres), C.byref(n), C.byref(g), C.byref(t), None, None))
+            time = t.value
+            if not pres.value:
+                continue
+            rec, groups = np.zeros((n.value, 16)), np.zeros((g.value, 10))
+            if rec.size or groups.size:
+                self._ck(self.L.mistark_sim_get_bending(self.h, kind, C.byref(pres), C.byref(n), C.byref(g), C.byref(t), ptr(rec), ptr(groups)))
+            kinds[name] = dict(rows=bending_rows_dict(rec, kind), groups=groups)
+        nodal = np.zeros((self.info().n_points, 6))
+        if nodal.size:
+            self._ck(self.L.mistark_sim_get_nodal_bending(self.h, nodal.ctypes.data))
+        return dict(kinds=kinds, nodal=nodal, time=time)
 
     # ---- contact recording -------------------------------------------------------------------------------------------------
     def record_contacts(self, on=True):
