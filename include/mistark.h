@@ -273,6 +273,40 @@ int mistark_nodal_bending(mistark_ctx* ctx, const int32_t* potentials, int32_t n
 /* out[g][10], g < n_groups; a declared group without rows reports zeros with -1 in slot 4. */
 int mistark_bending_group_report(mistark_ctx* ctx, int potential, const double* threshold, int32_t n_groups, double* out);
 
+/* ---- rigid-body wrench report -------------------------------------------------------------------------------------------------
+ * The free-body diagram of a rigid body: force and torque on it from any potential (rows) and from any family of potentials (bodies), at the current
+ * DoFs. Every rigid potential places a body through t1 = t0 + dt v1 and the normalised quaternion q0 + dt/2 (0, w1) q0, that is R1 = C(a) R0 with C the
+ * Cayley rotation of a = dt w1 / 2 in the world frame, so for any of them
+ *     F       = -(1/dt) dE/dv1
+ *     tau_com = -(1/dt) (I + [a]x + a a^T) dE/dw1          (torque about t1, world frame; N and N m with STARK's velocity DoFs)
+ * without a derivation per kind. mistark_forces returns -dE/dw1 / dt for a body's angular block: a generalised force on the angular-velocity DoF, which is
+ * the torque only while w1 dt is small. The report is the torque the solver balances, the exact virtual work of the potential as evaluated: for the lagged
+ * friction tables it need not equal r x ft of the friction report (mistark_contact.h): their contact-point velocity v1 + w1 x r1 reads w1 itself and is no
+ * pure function of the pose. The force is the report's ft; the torque is (I + [a]x + a a^T) (r1 x ft) + 2 r1 x (ft x a), off r1 x ft in first order of
+ * |a| (measured on the recorded scenes: up to 0.75 % of a table's largest r1 x ft at |a| = 5e-3).
+ * v1, w1, t0, q0: array ids of the bodies' state as mistark_rigid_budget takes them (v1, w1 DoF arrays of stride 3; all four with n_bodies items); dt is
+ * the one the first registered inertia potential has bound (EnergyRigidBodyInertia_Linear's, else EnergyLumpedInertia's, which serves a scene without
+ * bodies), read back once per call that launches. A pipeline of its own beside mistark_eval: nothing the evaluation, the solver or the contact detector
+ * owns is written, contact and friction tables are read as installed, no floating-point atomics (two reports of one state give the same bits), nothing is
+ * launched unless called. Single-rank accessor; refuses registration-only contexts, user-defined potentials, bad and duplicate ids.
+ *
+ * Rows. out[e][2][12], ids[e][4], rows as mistark_potential_element_forces has them. An element's DoF blocks are classed by block row as "v of body b",
+ * "w of body b" or "not rigid"; the blocks of one body are added in block order. Slot 0 is the body that appears first; a third body sets a flag and is
+ * dropped (no built-in potential has one). Per slot:
+ *   0..2 F | 3..5 tau_com | 6..8 arm F x tau_com / |F|^2: the point of the line of action nearest to the centre of mass, relative to t1 | 9 couple along F,
+ *   tau_com . F / |F| | 10 |F| | 11 |tau_com|   (6..9 are zero where |F| == 0)
+ * ids: 0 body of slot 0 or -1 | 1 body of slot 1 or -1 | 2 number of rigid blocks | 3 flags: +1 the element's condition is off (the record is zeros),
+ *   +2 more than two bodies, +4 a gradient block of a body is not finite
+ * A potential without a rigid block is legal: zeros with bodies -1. out and ids both NULL: n_rows alone, nothing is launched. */
+int mistark_potential_rigid_wrench(mistark_ctx* ctx, int potential, int v1, int w1, int t0, int q0, int32_t n_bodies, double* out, int32_t* ids, int64_t* n_rows);
+/* Bodies. Family f lists the potential ids families[family_start[f] .. family_start[f + 1]); an empty list means every potential: the unbalanced wrench,
+ * the body's Newton residual in N and N m. The generalised force of a family is formed by the force readout's nodal stage, so slots 0..2 and 9..11 are the
+ * bits mistark_forces returns with scale 1/dt for the body's v and w block. out[f][b][16]:
+ *   0..2 F | 3..5 tau_com | 6..8 torque about `about`, tau_com + (t1 - about) x F | 9..11 -dE/dw1 / dt as it came | 12..14 t1 | 15 |a|
+ * count[f][b]: the elements of the family whose condition is on and that touch the body (integers). Either output may be NULL. */
+int mistark_rigid_wrench(mistark_ctx* ctx, const int32_t* families, const int32_t* family_start, int32_t n_families, int v1, int w1, int t0, int q0, int32_t n_bodies,
+                         const double about[3], double* out, int32_t* count);
+
 /* ---- projection + assembly ------------------------------------------------------------------------------------------ */
 /* ElementHessians::project_to_PD_inplace__all / project_to_PD_for_update__selectively (ElementHessians.cpp:48-67,79-182;
  * project_to_PD.cpp:12-32). active_blocks: NULL = all elements, else ndofs/3 flags; only not-yet-projected elements
@@ -490,7 +524,8 @@ int mistark_sync(mistark_ctx* ctx);
  * that launched, mistark_contact.h; collision vertices of the last report summed by a whole wavefront), "friction_reports" / "friction_report_long_rows"
  * (the same two for the friction report), "constraint_reports" / "constraint_report_chunks" (constraint report calls that launched, chunks the last group
  * report was summed in), "bending_reports" / "bending_report_long_rows" / "bending_report_chunks" (bending report calls that launched, block rows of the
- * last nodal stage summed by a whole wavefront, chunks the last group stage was summed in). */
+ * last nodal stage summed by a whole wavefront, chunks the last group stage was summed in), "wrench_reports" / "wrench_long_rows" (wrench report calls
+ * that launched, rigid-body block rows of the last body report summed by a whole wavefront, over all its families). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

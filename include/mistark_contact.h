@@ -167,7 +167,8 @@ int mistark_contact_pair_report(mistark_ctx* ctx, double* out, int32_t* n_groups
  * the rigid side is A. Contact-point velocity of a side: the bary combination of its vertices' velocities (a rigid vertex: rb_v1 + rb_w1 x (R1 xloc));
  * u0 = T[0:3].v dt + 1.13e-9, u1 = T[3:6].v dt - 1.07e-9 (the reference's offsets), epsu = dt epsv; sticking iff |u| < epsu;
  * E = 0.5 (mu fn / epsu) |u|^2 sticking, mu fn (|u| - epsu / 2) sliding; force on A: ft = c (u0 T[0:3] + u1 T[3:6]), c = mu fn / epsu sticking,
- * mu fn / |u| sliding; on B: -ft. Torques on rigid bodies are not reported.
+ * mu fn / |u| sliding; on B: -ft. Torques on rigid bodies are not reported here: the wrench report (mistark.h, "rigid-body wrench
+ * report") gives the torque of every friction table on a body, as the exact virtual work of the lagged potential, which need not equal r x ft.
  * Rows come in key order = table order: the rows of table t (21..34, friction_d_d_pp_C0 .. friction_rb_d_tp_C0) are contiguous and line up with
  * mistark_contact_get_table's and mistark_contact_get_friction_data's.
  *   rows_i [n][8]:  0 table | 1 row in that table | 2 kind (0 pp, 1 pe, 2 pt, 3 ee, 4 ep, 5 tp) | 3 group of A | 4 group of B | 5 rigid body of A or -1 |

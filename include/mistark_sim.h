@@ -270,6 +270,21 @@ int mistark_sim_record_bending(mistark_sim* sim, int enabled, double threshold_r
 int mistark_sim_get_bending(mistark_sim* sim, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, double* time, double* rows, double* groups);
 /* points_out [n_points x 6]: the nodal records of both kinds together. */
 int mistark_sim_get_nodal_bending(mistark_sim* sim, double* points_out);
+/* Wrench recording (off by default; not in the reference), at the same place inside the step, after the Newton callbacks that precede an evaluation: one
+ * body report (mistark.h "rigid-body wrench report": per family and body a record of 16 doubles and an element count) over seven fixed families of
+ * potentials, in this order: linear inertia (EnergyRigidBodyInertia_Linear: with gravity and applied forces), angular inertia, the rb_constraint_* kinds,
+ * EnergyAttachments_rb_*, the contact_rb_* tables, the friction_rb_* tables, every potential (the unbalanced wrench: the body's Newton residual in N and
+ * N m). about: the reference point of slots 6..8 (NULL: the origin). Results stay on the device until they are asked for. With recording off nothing is
+ * launched or allocated. A scene without rigid bodies reports n_bodies = 0. */
+int mistark_sim_record_wrench(mistark_sim* sim, int enabled, const double about[3]);
+/* The report of the last accepted step. Every output is nullable; a first call with records and counts NULL gives the sizes and downloads nothing.
+ * records [n_families x n_bodies x 16], counts [n_families x n_bodies], labels: the bodies' labels, one per line, labels_bytes with the terminator. */
+/* What a step records with, for direct calls of mistark_rigid_wrench on mistark_sim_engine(): state = array ids {v1, w1, t0, q0} and the body count;
+ * family_start [8] and families (nullable; family_start[7] entries): the potential ids of the seven families in CSR form. The seventh list is empty, which
+ * mistark_rigid_wrench reads as every potential; so it reads any other family that is empty in this scene, which a step records as the zero wrench. The
+ * scene must be registered (mistark_sim_prepare or a first step). */
+int mistark_sim_wrench_sources(mistark_sim* sim, int32_t state[5], int32_t family_start[8], int32_t* families);
+int mistark_sim_get_wrench(mistark_sim* sim, int32_t* n_families, int32_t* n_bodies, int64_t* labels_bytes, double* time, double* records, int32_t* counts, char* labels);
 /* Contact recording (off by default; not in the reference), at the same place inside the step: one contact report of the end-of-step state
  * (mistark_contact.h "contact report": the rows of the installed barrier tables, the vertex records, the group-pair records), after the Newton callbacks
  * that precede an evaluation, so that the installed tables are that state's. Results stay on the device until they are asked for. With recording off

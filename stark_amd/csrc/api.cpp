@@ -589,6 +589,8 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "bending_reports") *out = c.n_bending_reports;
     else if (n == "bending_report_long_rows") *out = bending_long_rows(c);
     else if (n == "bending_report_chunks") *out = c.n_bending_chunks;
+    else if (n == "wrench_reports") *out = c.n_wrench_reports;
+    else if (n == "wrench_long_rows") *out = wrench_long_rows(c);
     else if (n == "contact_reports") *out = c.n_contact_reports;
     else if (n == "contact_report_long_rows") *out = contact_report_long_rows(c);
     else if (n == "friction_reports") *out = c.n_friction_reports;
@@ -778,6 +780,21 @@ int mistark_bending_group_report(mistark_ctx* ctx, int potential, const double* 
 {
     API_BEGIN
     bending_groups_host(ctx->c, potential, threshold, n_groups, out);
+    API_END(0)
+}
+
+// ---- rigid-body wrench report (wrench.hip) -------------------------------------------------------------------------------------
+int mistark_potential_rigid_wrench(mistark_ctx* ctx, int potential, int v1, int w1, int t0, int q0, int32_t n_bodies, double* out, int32_t* ids, int64_t* n_rows)
+{
+    API_BEGIN
+    wrench_rows_host(ctx->c, potential, v1, w1, t0, q0, n_bodies, out, ids, n_rows);
+    API_END(0)
+}
+int mistark_rigid_wrench(mistark_ctx* ctx, const int32_t* families, const int32_t* family_start, int32_t n_families, int v1, int w1, int t0, int q0, int32_t n_bodies,
+                         const double about[3], double* out, int32_t* count)
+{
+    API_BEGIN
+    wrench_bodies_host(ctx->c, families, family_start, n_families, v1, w1, t0, q0, n_bodies, about, out, count);
     API_END(0)
 }
 
@@ -1603,6 +1620,19 @@ int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows)
 {
     API_BEGIN
     mistark::bending_fetch_nodal(ctx->c, out, n_rows);
+    API_END(0)
+}
+int wrench_record(mistark_ctx* ctx, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,
+                  const double about[3])
+{
+    API_BEGIN
+    wrench_record_step(ctx->c, families, all, v1, w1, t0, q0, n_bodies, about);
+    API_END(0)
+}
+int wrench_fetch(mistark_ctx* ctx, int32_t n_families, int32_t n_bodies, double* out, int32_t* count)
+{
+    API_BEGIN
+    wrench_fetch_step(ctx->c, n_families, n_bodies, out, count);
     API_END(0)
 }
 int budget_fetch(mistark_ctx* ctx, int slot, double* out, int64_t n)

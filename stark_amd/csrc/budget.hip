@@ -245,6 +245,17 @@ void budget_inertia(Context& c, int pot, const double* about, int32_t n_groups, 
     budget_finish(c, slot, dst, launch, n_out, out_host);
 }
 
+// dt and gravity as the first registered inertia potential has them bound: EnergyRigidBodyInertia_linear's bindings 7 and 8, EnergyLumpedInertia's 9 and 10
+InertiaBindings inertia_bindings(const Context& c)
+{
+    for (const Potential& P : c.pots) {
+        if (P.kind == KIND_CUSTOM) continue;
+        if (P.name == E_RBInertiaLinear::name) return {P.args.arr[7], P.args.arr[8]};
+        if (P.name == E_LumpedInertia::name) return {P.args.arr[9], P.args.arr[10]};
+    }
+    return {};
+}
+
 void budget_rigid(Context& c, int t0, int q0, int v1, int w1, int mass, int J_loc, int32_t n_bodies, const double* about, double* out_host, int slot)
 {
     const char* who = "mistark_rigid_budget";
@@ -262,12 +273,8 @@ void budget_rigid(Context& c, int t0, int q0, int v1, int w1, int mass, int J_lo
     const double* d_m = budget_array(c, mass, 1, n_bodies, "mass", who);
     const double* d_J = budget_array(c, J_loc, 9, n_bodies, "J_loc", who);
     // dt and gravity as the inertia potentials have them bound
-    const double *d_dt = nullptr, *d_g = nullptr;
-    for (const Potential& P : c.pots) {
-        if (P.kind == KIND_CUSTOM || d_dt) continue;
-        if (P.name == E_RBInertiaLinear::name) d_dt = P.args.arr[7], d_g = P.args.arr[8];
-        else if (P.name == E_LumpedInertia::name) d_dt = P.args.arr[9], d_g = P.args.arr[10];
-    }
+    const InertiaBindings ib = inertia_bindings(c);
+    const double *d_dt = ib.dt, *d_g = ib.gravity;
     if (!d_dt || !d_g) throw Error(std::string(who) + ": no inertia potential is registered: the time step and gravity are taken from its bindings");
     const size_t n_out = (size_t)BUDGET_REC * n_bodies;
     double* dst = budget_target(c, slot, c.bg_out, n_out);

@@ -685,7 +685,21 @@ struct Context
     int64_t n_bending_chunks = 0;      // counter "bending_report_chunks": chunks of the last group stage
     bool bdr_stat_valid = false;
 
-    int last_cg_iters = 0;          // iteration count of the previous solve (first-batch predictor)
+    // Rigid-body wrench report (wrench.hip): the eighth pipeline beside eval(). The force readout's two stages on buffers of its own (wr_pool: node
+    // gradients, wr_key.. : the key sort, wr_f [family][ndofs]: the generalised forces of every family), row records field-major in wr_rec
+    // ([2 * 12][rows]) with wr_ids [rows][4], body records wr_out [family][body][16] and integer counts wr_count [family][body]. Nothing but these
+    // buffers is written.
+    DevBuf<double> wr_pool, wr_elemE, wr_f, wr_rec, wr_out;
+    DevBuf<uint32_t> wr_key, wr_key_alt, wr_val, wr_val_alt;
+    DevBuf<uint32_t> wr_stat;          // per family of the last body report: [0] rows a whole wavefront summed, [1] the rigid ones among them
+    DevBuf<unsigned char> wr_desc;
+    DevBuf<uint8_t> wr_cub_tmp, wr_active;  // wr_active: per row of a conditional potential, whether its condition is on
+    DevBuf<int32_t> wr_ids, wr_count;
+    int wr_stat_families = 0;          // families wr_stat holds (0: no body report yet)
+    int32_t wr_out_families = 0, wr_out_bodies = 0;  // what wr_out / wr_count hold of the last body report
+    int64_t n_wrench_reports = 0;      // counter "wrench_reports": calls that launched
+
+    int last_cg_iters = 0;         // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
 
@@ -865,6 +879,21 @@ int64_t bending_long_rows(Context& c);  // counter "bending_report_long_rows"
 void bending_record_step(Context& c, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups);  // into Context::bdr_slot; -1: not registered
 void bending_fetch_kind(Context& c, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups);
 void bending_fetch_nodal(Context& c, double* out, int64_t n_rows);
+// Rigid-body wrench report (wrench.hip, records as wrench.hpp lays them out). v1, w1, t0, q0: array ids of the bodies' state. Null outputs are skipped.
+void wrench_rows_host(Context& c, int pot, int v1, int w1, int t0, int q0, int32_t n_bodies, double* out, int32_t* ids, int64_t* n_rows);
+void wrench_bodies_host(Context& c, const int32_t* families, const int32_t* family_start, int32_t n_families, int v1, int w1, int t0, int q0, int32_t n_bodies, const double* about,
+                        double* out, int32_t* count);
+int64_t wrench_long_rows(Context& c);  // counter "wrench_long_rows"
+// ... for the host mirror: the body report of the given families (an empty list: the zero wrench, unless all[f]: every potential) kept in wr_out / wr_count
+void wrench_record_step(Context& c, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,
+                        const double* about);
+void wrench_fetch_step(Context& c, int32_t n_families, int32_t n_bodies, double* out, int32_t* count);
+// device addresses of dt and gravity as the first registered inertia potential has them bound (budget.hip; null: none is registered)
+struct InertiaBindings
+{
+    const double *dt = nullptr, *gravity = nullptr;
+};
+InertiaBindings inertia_bindings(const Context& c);
 int find_kind(const char* name);
 int kind_nb(int kind);
 int kind_nbind(int kind);

@@ -9,6 +9,7 @@
 // No floating-point atomics anywhere: two readouts of one state give the same bits.
 #include "kernels_common.hpp"
 #include "force_keys.hpp"
+#include "force_stage.hpp"
 
 namespace mistark {
 
@@ -136,19 +137,11 @@ std::vector<int> select_potentials(Context& c, const int32_t* pots, int32_t n, b
     return ids;
 }
 
-namespace {
-struct Selection
-{
-    std::vector<int> pots;           // selected potentials with elements, in the caller's order
-    std::vector<ForceDesc> descs;
-    std::vector<int64_t> g_off;
-    int64_t total = 0;               // contributions (element, block)
-};
-// the selection and its layout in the readout pool
-Selection select(Context& c, const int32_t* pots, int32_t n, bool all, const char* who)
+// the selection and its layout in a readout pool
+ForceSelection force_select(Context& c, const int32_t* pots, int32_t n, bool all, const char* who)
 {
     const std::vector<int> ids = select_potentials(c, pots, n, all, who);
-    Selection S;
+    ForceSelection S;
     for (int p : ids) {
         const Potential& P = c.pots[(size_t)p];
         if (P.n_elem <= 0) continue;  // (empty tables launch nothing)
@@ -170,44 +163,58 @@ Selection select(Context& c, const int32_t* pots, int32_t n, bool all, const cha
     if (S.total >= (1ll << 31)) throw Error(std::string(who) + ": too many contributions");
     return S;
 }
-// stage 1: node gradients of every selected element into c.fr_pool
-void element_stage(Context& c, const Selection& S)
+// stage 1: node gradients of every selected element into W.pool
+void force_element_stage(Context& c, const ForceSelection& S, const ForceWork& W)
 {
     int n_max = 0;
     for (int p : S.pots) n_max = std::max(n_max, c.pots[(size_t)p].n_elem);
-    c.fr_pool.ensure(3 * (size_t)S.total);
-    c.fr_elemE.ensure((size_t)n_max);
-    for (size_t k = 0; k < S.pots.size(); k++) launch_force_elements(c, c.pots[(size_t)S.pots[k]], c.fr_pool.p + 3 * (size_t)S.g_off[k], c.fr_elemE.p);
+    W.pool.ensure(3 * (size_t)S.total);
+    W.elemE.ensure((size_t)n_max);
+    for (size_t k = 0; k < S.pots.size(); k++) launch_force_elements(c, c.pots[(size_t)S.pots[k]], W.pool.p + 3 * (size_t)S.g_off[k], W.elemE.p);
     MS_CHECK(hipGetLastError());
-    c.n_force_readouts++;
 }
-// stage 2: f_dev[ndofs] = -scale * row sums of the pool
-void nodal_stage(Context& c, const Selection& S, double scale, double* f_dev)
+// stage 2: f_dev[ndofs] = -scale * row sums of the pool; stat[0] = rows a whole wavefront summed. Returns the sorted keys (one of W.key / W.key_alt).
+const uint32_t* force_nodal_stage(Context& c, const ForceSelection& S, const ForceWork& W, double scale, double* f_dev, uint32_t* stat)
 {
     const int64_t n = S.total;
-    c.fr_key.ensure((size_t)n);
-    c.fr_key_alt.ensure((size_t)n);
-    c.fr_val.ensure((size_t)n);
-    c.fr_val_alt.ensure((size_t)n);
-    c.fr_stat.ensure(2);
-    c.fr_desc.ensure(S.descs.size() * sizeof(ForceDesc));
-    h2d_small(c, c.fr_desc.p, S.descs.data(), S.descs.size() * sizeof(ForceDesc));
-    hipLaunchKernelGGL(k_force_keys, dim3(grid_for(n)), dim3(BLOCK), 0, c.stream, (const ForceDesc*)c.fr_desc.p, (int)S.descs.size(), n, c.fr_key.p, c.fr_val.p);
+    W.key.ensure((size_t)n);
+    W.key_alt.ensure((size_t)n);
+    W.val.ensure((size_t)n);
+    W.val_alt.ensure((size_t)n);
+    W.desc.ensure(S.descs.size() * sizeof(ForceDesc));
+    h2d_small(c, W.desc.p, S.descs.data(), S.descs.size() * sizeof(ForceDesc));
+    hipLaunchKernelGGL(k_force_keys, dim3(grid_for(n)), dim3(BLOCK), 0, c.stream, (const ForceDesc*)W.desc.p, (int)S.descs.size(), n, W.key.p, W.val.p);
     int bits = 1;
     while (bits < 32 && (1ll << bits) <= c.nbr) bits++;
     size_t tmp = 0;
-    hipcub::DoubleBuffer<uint32_t> dk(c.fr_key.p, c.fr_key_alt.p), dv(c.fr_val.p, c.fr_val_alt.p);
+    hipcub::DoubleBuffer<uint32_t> dk(W.key.p, W.key_alt.p), dv(W.val.p, W.val_alt.p);
     MS_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, dk, dv, (int)n, 0, bits, c.stream));
-    c.fr_cub_tmp.ensure(tmp);
-    MS_CHECK(hipcub::DeviceRadixSort::SortPairs(c.fr_cub_tmp.p, tmp, dk, dv, (int)n, 0, bits, c.stream));  // (stable: equal rows keep the contribution order)
+    W.cub_tmp.ensure(tmp);
+    MS_CHECK(hipcub::DeviceRadixSort::SortPairs(W.cub_tmp.p, tmp, dk, dv, (int)n, 0, bits, c.stream));  // (stable: equal rows keep the contribution order)
     {
         FillQueue fills(c.stream);
         fills.add(f_dev, 0, (size_t)c.ndofs * sizeof(double));  // (rows with nobody contributing are zero)
-        fills.add(c.fr_stat.p, 0, 2 * sizeof(uint32_t));
+        fills.add(stat, 0, 2 * sizeof(uint32_t));
     }
-    hipLaunchKernelGGL(k_force_segsum, dim3(grid_for(n)), dim3(BLOCK), 0, c.stream, (const uint32_t*)dk.Current(), (const uint32_t*)dv.Current(), n, (const double*)c.fr_pool.p, scale,
-                       f_dev, c.fr_stat.p);
+    hipLaunchKernelGGL(k_force_segsum, dim3(grid_for(n)), dim3(BLOCK), 0, c.stream, (const uint32_t*)dk.Current(), (const uint32_t*)dv.Current(), n, (const double*)W.pool.p, scale,
+                       f_dev, stat);
     MS_CHECK(hipGetLastError());
+    return dk.Current();
+}
+
+namespace {
+using Selection = ForceSelection;
+Selection select(Context& c, const int32_t* pots, int32_t n, bool all, const char* who) { return force_select(c, pots, n, all, who); }
+ForceWork own_work(Context& c) { return ForceWork{c.fr_pool, c.fr_elemE, c.fr_key, c.fr_key_alt, c.fr_val, c.fr_val_alt, c.fr_desc, c.fr_cub_tmp}; }
+void element_stage(Context& c, const Selection& S)
+{
+    force_element_stage(c, S, own_work(c));
+    c.n_force_readouts++;
+}
+void nodal_stage(Context& c, const Selection& S, double scale, double* f_dev)
+{
+    c.fr_stat.ensure(2);
+    force_nodal_stage(c, S, own_work(c), scale, f_dev, c.fr_stat.p);
     c.fr_stat_valid = true;
 }
 }  // namespace

@@ -36,6 +36,11 @@ int constraint_fetch(mistark_ctx* ctx, int kind, double* out, double* aux, int32
 int bending_record(mistark_ctx* ctx, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups);
 int bending_fetch(mistark_ctx* ctx, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups);
 int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows);
+// rigid-body wrench report (wrench.hip): the body report of the given families of potentials (an empty list: the zero wrench, unless all[f]: every
+// potential) kept on the device; out [n_families][n_bodies][16], count [n_families][n_bodies]
+int wrench_record(mistark_ctx* ctx, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,
+                  const double about[3]);
+int wrench_fetch(mistark_ctx* ctx, int32_t n_families, int32_t n_bodies, double* out, int32_t* count);
 // contact report (contact_report.hip) of the current state into the device set of the host mirror; its three parts (null outputs are skipped, the counts
 // always come back)
 int contact_report_record(mistark_ctx* ctx);

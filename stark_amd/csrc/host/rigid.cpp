@@ -172,6 +172,7 @@ void EnergyRigidBodyInertia::register_potentials(mistark_ctx* ctx)
         B.add_id(stark.dt_array(), 1, -1);
         B.potential("EnergyRigidBodyInertia_Angular", conn);
     }
+    stark.wrench_source = {rb->id_t0, rb->id_q0_, rb->id_v1, rb->id_w1, (int)n, &labels};  // (wrench recording: ids only, nothing is registered for it)
     if (stark.budget_recording) {
         // budget recording: the rigid budget reads J_loc on the device (bound by no potential: registered only while recording is on)
         stark.check(id_J_loc = mistark_array(ctx, J_loc[0].data(), n, 9));

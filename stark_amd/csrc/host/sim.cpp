@@ -62,6 +62,8 @@ void Stark::ensure_registered()
     constraint_sources.clear();
     bending_recorded = false;
     bending_source = BendingSource{};
+    wrench_recorded = false;
+    wrench_source = WrenchSource{};
     contact_labels = nullptr;
     budget_inertia_sources.clear();
     budget_rigid_source = BudgetRigidSource{};
@@ -258,6 +260,20 @@ bool Stark::run_one_step()
             bending_recorded_source = src;
             bending_time = current_time + dt;
             bending_recorded = true;
+        }
+        if (wrench_recording) {
+            for (auto& f : n.before_energy_evaluation) f();  // (as force recording: the installed contact tables are then this state's)
+            const WrenchSource& r = wrench_source;
+            if (r.n > 0) {
+                std::vector<std::vector<int32_t>> families;
+                wrench_sources(families);
+                std::vector<char> all((size_t)WRENCH_FAMILIES, 0);
+                all.back() = 1;
+                check(wrench_record(ctx, families, all, r.v1, r.w1, r.t0, r.q0, r.n, wrench_about.data()));
+            }
+            wrench_bodies = r.n;
+            wrench_time = current_time + dt;
+            wrench_recorded = true;
         }
         for (auto& f : callbacks->on_time_step_accepted) f();  // Stark.cpp:164-170
         for (auto& f : callbacks->after_time_step) f();
@@ -463,6 +479,37 @@ void Stark::get_nodal_bending(double* points_out)
     const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
     if (r0 < 0) throw std::runtime_error("get_nodal_bending: the point set has no DoFs");
     std::copy(all.begin() + 6 * r0, all.begin() + 6 * (r0 + force_n_points), points_out);
+}
+void Stark::record_wrench(bool enabled, const Vec3& about)
+{
+    for (double a : about)
+        if (!std::isfinite(a)) throw std::runtime_error("record_wrench: the reference point is not finite");
+    wrench_recording = enabled;
+    wrench_about = about;
+    wrench_recorded = false;
+}
+std::array<int32_t, 5> Stark::wrench_sources(std::vector<std::vector<int32_t>>& families)
+{
+    if (!ctx) throw std::runtime_error("wrench_sources: the scene is not registered yet");
+    families.assign((size_t)WRENCH_FAMILIES, {});
+    for (int f = 0; f + 1 < WRENCH_FAMILIES; f++) check(force_potentials_by_prefix(ctx, wrench_family_prefix[f], families[(size_t)f]));
+    const WrenchSource& r = wrench_source;
+    return {r.v1, r.w1, r.t0, r.q0, r.n};
+}
+void Stark::get_wrench(WrenchReport& out, bool sizes_only)
+{
+    if (!wrench_recording) throw std::runtime_error("get_wrench: wrench recording is off (record_wrench)");
+    if (!ctx || !wrench_recorded) throw std::runtime_error("get_wrench: no time step has been accepted since recording was switched on");
+    out = WrenchReport{};
+    out.time = wrench_time;
+    out.n_bodies = wrench_bodies;
+    if (out.n_bodies <= 0) return;
+    const std::vector<std::string>* labels = wrench_source.labels;
+    for (int32_t b = 0; b < out.n_bodies; b++) out.labels.push_back(labels && (size_t)b < labels->size() ? (*labels)[(size_t)b] : "");
+    if (sizes_only) return;
+    out.records.resize((size_t)WRENCH_FAMILIES * out.n_bodies * 16);
+    out.counts.resize((size_t)WRENCH_FAMILIES * out.n_bodies);
+    check(wrench_fetch(ctx, WRENCH_FAMILIES, out.n_bodies, out.records.data(), out.counts.data()));
 }
 void Stark::record_friction(bool enabled)
 {

@@ -265,6 +265,35 @@ public:
         int32_t n_groups = 0;
     };
     BendingSource bending_source;
+    // Wrench recording (off by default; not in the reference): at the same place, after the before_energy_evaluation callbacks, one body report of the
+    // rigid-body wrench report (include/mistark.h "rigid-body wrench report": per family and body a record of 16 doubles and an element count) over
+    // seven fixed families of potentials, kept on the device until get_wrench() downloads it. Off: nothing is launched or allocated. A scene without
+    // rigid bodies records nothing and reports empty arrays.
+    static constexpr int WRENCH_FAMILIES = 7;
+    // registry-name prefixes of the families; the last, empty one is every potential: the unbalanced wrench
+    static constexpr const char* wrench_family_prefix[WRENCH_FAMILIES] = {"EnergyRigidBodyInertia_Linear", "EnergyRigidBodyInertia_Angular", "rb_constraint_", "EnergyAttachments_rb_",
+                                                                          "contact_rb_", "friction_rb_", ""};
+    struct WrenchReport
+    {
+        int32_t n_bodies = 0;
+        std::vector<double> records;      // [WRENCH_FAMILIES][n_bodies][16]
+        std::vector<int32_t> counts;      // [WRENCH_FAMILIES][n_bodies]
+        std::vector<std::string> labels;  // per body
+        double time = 0.0;                // simulation time of the accepted step
+    };
+    void record_wrench(bool enabled, const Vec3& about = {0.0, 0.0, 0.0});
+    void get_wrench(WrenchReport& out, bool sizes_only = false);  // sizes_only: count, labels and time; nothing is downloaded
+    // what a step records with, for direct calls of mistark_rigid_wrench on the engine: the potential ids of the first six families (the seventh is every
+    // potential) and the array ids {v1, w1, t0, q0} with the body count
+    std::array<int32_t, 5> wrench_sources(std::vector<std::vector<int32_t>>& families);
+    bool wrench_recording = false, wrench_recorded = false;
+    // what the rigid-body inertia notes while it registers: the array ids of the bodies' state, their number and labels
+    struct WrenchSource
+    {
+        int t0 = -1, q0 = -1, v1 = -1, w1 = -1, n = 0;
+        const std::vector<std::string>* labels = nullptr;
+    };
+    WrenchSource wrench_source;
     // DoF sets of the dynamics (set index, block rows), noted by their register_dofs: where get_forces finds the rows of points and bodies
     int force_set_points = -1, force_set_rb_v = -1, force_set_rb_w = -1;
     int64_t force_n_points = 0, force_n_rb = 0;
@@ -282,6 +311,9 @@ private:
     double budget_time = 0.0, contacts_time = 0.0, friction_time = 0.0, constraints_time = 0.0;
     Vec3 constraint_about = {0.0, 0.0, 0.0};
     double bending_threshold = 0.0, bending_time = 0.0;
+    Vec3 wrench_about = {0.0, 0.0, 0.0};
+    double wrench_time = 0.0;
+    int32_t wrench_bodies = 0;  // bodies of the report recorded at the last accepted step
     BendingSource bending_recorded_source;  // ... as recorded at the last accepted step
     struct ConstraintRecorded  // per kind code, as recorded at the last accepted step
     {

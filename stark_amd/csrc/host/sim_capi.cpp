@@ -924,6 +924,43 @@ int mistark_sim_get_nodal_bending(mistark_sim* s, double* points_out)
     s->sim->get_stark().get_nodal_bending(points_out);
     SIM_END
 }
+int mistark_sim_record_wrench(mistark_sim* s, int enabled, const double about[3])
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_wrench(enabled != 0, about ? Vec3{about[0], about[1], about[2]} : Vec3{0.0, 0.0, 0.0});
+    SIM_END
+}
+int mistark_sim_wrench_sources(mistark_sim* s, int32_t state[5], int32_t family_start[8], int32_t* families)
+{
+    SIM_BEGIN
+    std::vector<std::vector<int32_t>> fam;
+    const std::array<int32_t, 5> st = s->sim->get_stark().wrench_sources(fam);
+    if (state) std::copy(st.begin(), st.end(), state);
+    int32_t n = 0;
+    for (size_t f = 0; f < fam.size(); f++) {
+        if (family_start) family_start[f] = n;
+        if (families) std::copy(fam[f].begin(), fam[f].end(), families + n);
+        n += (int32_t)fam[f].size();
+    }
+    if (family_start) family_start[fam.size()] = n;
+    SIM_END
+}
+int mistark_sim_get_wrench(mistark_sim* s, int32_t* n_families, int32_t* n_bodies, int64_t* labels_bytes, double* time, double* records, int32_t* counts, char* labels)
+{
+    SIM_BEGIN
+    Stark::WrenchReport r;
+    s->sim->get_stark().get_wrench(r, !records && !counts);  // (the size query downloads nothing)
+    std::string lb;
+    for (const auto& l : r.labels) lb += l + "\n";
+    if (n_families) *n_families = Stark::WRENCH_FAMILIES;
+    if (n_bodies) *n_bodies = r.n_bodies;
+    if (labels_bytes) *labels_bytes = (int64_t)lb.size() + 1;
+    if (time) *time = r.time;
+    if (records) std::copy(r.records.begin(), r.records.end(), records);
+    if (counts) std::copy(r.counts.begin(), r.counts.end(), counts);
+    if (labels) std::memcpy(labels, lb.c_str(), lb.size() + 1);
+    SIM_END
+}
 int mistark_sim_begin_time_step(mistark_sim* s)
 {
     SIM_BEGIN

@@ -452,6 +452,32 @@ class Engine:
                                                         out.ctypes.data if out.size else None))
         return out
 
+    # ---- rigid-body wrench report (include/mistark.h "rigid-body wrench report") -------------------------------------------
+    def rigid_wrench_rows(self, pid: int, v1, w1, t0, q0, n_bodies: int):
+        """(records [n_elem, 2, 12], ids [n_elem, 4]) of one potential: per element and body slot F, tau_com, arm, couple along F, |F|, |tau_com|; ids:
+        body of slot 0 and 1 (-1: none), number of rigid blocks, flags. v1, w1, t0, q0: array ids of the bodies' state."""
+        n = C.c_int64()
+        args = (int(pid), int(v1), int(w1), int(t0), int(q0), int(n_bodies))
+        self._ck(self.L.mistark_potential_rigid_wrench(self.h, *args, None, None, C.byref(n)))
+        rec, ids = np.zeros((n.value, 2, 12)), np.zeros((n.value, 4), dtype=np.int32)
+        if n.value:
+            self._ck(self.L.mistark_potential_rigid_wrench(self.h, *args, rec.ctypes.data, ids.ctypes.data, C.byref(n)))
+        return rec, ids
+
+    def rigid_wrench(self, families, v1, w1, t0, q0, n_bodies: int, about=(0.0, 0.0, 0.0)):
+        """(records [n_families, n_bodies, 16], counts [n_families, n_bodies]) for families of potential ids (a list of lists; an empty list: every
+        potential, the unbalanced wrench): F, tau_com, torque about `about`, -dE/dw1 / dt, t1, |a|; counts: active elements touching the body."""
+        fams = [np.ascontiguousarray([] if f is None else f, dtype=np.int32).reshape(-1) for f in families]
+        start = np.zeros(len(fams) + 1, dtype=np.int32)
+        start[1:] = np.cumsum([f.size for f in fams])
+        flat = np.ascontiguousarray(np.concatenate(fams) if fams else [], dtype=np.int32)
+        ab = np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        out = np.zeros((len(fams), int(n_bodies), 16))
+        cnt = np.zeros((len(fams), int(n_bodies)), dtype=np.int32)
+        self._ck(self.L.mistark_rigid_wrench(self.h, flat.ctypes.data if flat.size else None, start.ctypes.data, len(fams), int(v1), int(w1), int(t0), int(q0),
+                                             int(n_bodies), ab.ctypes.data, out.ctypes.data if out.size else None, cnt.ctypes.data if cnt.size else None))
+        return out, cnt
+
     # ---- bending report (include/mistark.h "bending report") ---------------------------------------------------------------
     @staticmethod
     def _thresholds(threshold, n_groups, who):

@@ -148,6 +148,9 @@ def _lib():
         L.mistark_sim_record_bending.argtypes = [p, C.c_int, C.c_double]
         L.mistark_sim_get_bending.argtypes = [p, C.c_int, I32, I64, I32, D, p, p]
         L.mistark_sim_get_nodal_bending.argtypes = [p, p]
+        L.mistark_sim_record_wrench.argtypes = [p, C.c_int, p]
+        L.mistark_sim_wrench_sources.argtypes = [p, p, p, p]
+        L.mistark_sim_get_wrench.argtypes = [p, I32, I32, I64, D, p, p, p]
         L.mistark_sim_record_friction.argtypes = [p, C.c_int]
         L.mistark_sim_get_friction.argtypes = [p, I64, I64, I32, I64, D, p, p, p, p, p, p, p]
         _bound = True
@@ -627,6 +630,38 @@ class Simulation:
         if nodal.size:
             self._ck(self.L.mistark_sim_get_nodal_bending(self.h, nodal.ctypes.data))
         return dict(kinds=kinds, nodal=nodal, time=time)
+
+    # ---- wrench recording ------------------------------------------------------------------------------------------------------
+    WRENCH_FAMILIES = ("inertia_linear", "inertia_angular", "constraints", "attachments", "contact", "friction", "all")
+
+    def record_wrench(self, on=True, about=(0.0, 0.0, 0.0)):
+        """Every accepted step then keeps the rigid-body wrench report of the state it converged at on the device: per body the force and torque of
+        seven families of potentials (WRENCH_FAMILIES; "inertia_linear" holds gravity and applied forces, "all" is the unbalanced wrench)."""
+        ab = np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        self._ck(self.L.mistark_sim_record_wrench(self.h, int(bool(on)), ab.ctypes.data))
+
+    def wrench_sources(self):
+        """What a step records with, for direct calls of Engine.rigid_wrench on the simulation's engine: dict(v1, w1, t0, q0 (array ids), n_bodies,
+        families={name: potential ids}); "all" is the empty list, and so is every family the scene has no potential of (a step records zeros for those,
+        Engine.rigid_wrench reads an empty list as every potential)."""
+        state, start = np.zeros(5, dtype=np.int32), np.zeros(8, dtype=np.int32)
+        self._ck(self.L.mistark_sim_wrench_sources(self.h, state.ctypes.data, start.ctypes.data, None))
+        flat = np.zeros(max(int(start[7]), 1), dtype=np.int32)
+        self._ck(self.L.mistark_sim_wrench_sources(self.h, state.ctypes.data, start.ctypes.data, flat.ctypes.data))
+        fams = {name: [int(x) for x in flat[start[k]:start[k + 1]]] for k, name in enumerate(self.WRENCH_FAMILIES)}
+        return dict(v1=int(state[0]), w1=int(state[1]), t0=int(state[2]), q0=int(state[3]), n_bodies=int(state[4]), families=fams)
+
+    def wrench(self):
+        """The wrench report of the last accepted step: dict(families=WRENCH_FAMILIES, records [7, n_bodies, 16] and counts [7, n_bodies] as
+        Engine.rigid_wrench() gives them, labels (one per body), time). Raises while recording is off."""
+        nf, nb, lb, t = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double()
+        self._ck(self.L.mistark_sim_get_wrench(self.h, C.byref(nf), C.byref(nb), C.byref(lb), C.byref(t), None, None, None))
+        rec, cnt = np.zeros((nf.value, nb.value, 16)), np.zeros((nf.value, nb.value), dtype=np.int32)
+        buf = C.create_string_buffer(max(int(lb.value), 1))
+        if nb.value:
+            self._ck(self.L.mistark_sim_get_wrench(self.h, C.byref(nf), C.byref(nb), C.byref(lb), C.byref(t), rec.ctypes.data, cnt.ctypes.data, buf))
+        labels = buf.value.decode().split("\n")[:nb.value]
+        return dict(families=self.WRENCH_FAMILIES, records=rec, counts=cnt, labels=labels, time=t.value)
 
     # ---- contact recording -------------------------------------------------------------------------------------------------
     def record_contacts(self, on=True):
