@@ -273,6 +273,35 @@ int mistark_nodal_bending(mistark_ctx* ctx, const int32_t* potentials, int32_t n
 /* out[g][10], g < n_groups; a declared group without rows reports zeros with -1 in slot 4. */
 int mistark_bending_group_report(mistark_ctx* ctx, int potential, const double* threshold, int32_t n_groups, double* out);
 
+/* ---- Hessian spectrum report ---------------------------------------------------------------------------------------------------
+ * Where indefiniteness sits: the eigenvalues of every element Hessian of a potential and what mistark_project would make of them, per element, per block
+ * row and per potential, without eigenvectors and without changing a bit of the Hessians, the gradient, the matrix or anything a solver owns. A pipeline
+ * of its own beside mistark_eval, like the readouts above: it writes only buffers of its own, uses no floating-point atomics and launches nothing unless
+ * it is called; two reports of one state give the same bits.
+ * source 0: the element-Hessian pool as it stands, that is the state after mistark_eval(MISTARK_EVAL_P_G_H), before or after mistark_project. Any
+ *   potential qualifies, user-defined ones included. Refused when no Hessians have been evaluated, and for a potential whose current Hessians are the
+ *   float blocks of the lazy path (option lazy_eval).
+ * source 1: a fresh evaluation at the current DoFs with the generic kernel of the potential's kind, into a pool of the report's own (one potential at a
+ *   time: 72 NB^2 bytes per element of the largest). Refuses user-defined potentials and sharded contexts with the force readout's messages. With option
+ *   force_generic = 1 the evaluation's own Hessians come from the same kernel, and source 1 equals source 0 to the bit.
+ * Also refused: registration-only contexts, bad or duplicate ids, any other source.
+ * The eigenvalues come from the projection's own iteration (cyclic-by-round Jacobi, the same pair schedule, stop rule off <= 1e-24 ||H||_F^2, at most 30
+ * sweeps, the same guard on tiny off-diagonal entries), so the test `l < eps` is decided as mistark_project decides it, up to rounding.
+ * Element record, 10 doubles: 0 lambda_min | 1 lambda_max | 2 eigenvalues < eps | 3 eigenvalues < 0 | 4 deficit sqrt(sum_{l < eps} (eps - l)^2), the
+ *   Frobenius norm of what a clamping projection adds | 5 ||H||_F of the stored entries | 6 trace of the stored diagonal | 7 sweeps run | 8 sqrt(off) at
+ *   the stop: by Weyl every sorted eigenvalue is within this of a true one, up to rounding | 9 flags: +1 field 2 > 0 (mistark_project would change the
+ *   element), +2 a stored entry is not finite (fields 0..8 and the spectrum are zeros), +4 not converged in 30 sweeps.
+ * Nodal record, 5 doubles per block row: 0 elements touching the row | 1 of them flagged +1 | 2 smallest lambda_min among the finite ones (0 where none)
+ *   | 3 sum of deficit^2 | 4 potential id holding the smallest (-1 where none; the first in the order of the list, then of the elements).
+ * Potential record, 10 doubles: 0 elements | 1 flagged +1 | 2 with lambda_min < 0 | 3 non-finite | 4 not converged | 5 smallest lambda_min | 6 first
+ *   element attaining it (-1: none) | 7 largest lambda_max | 8 sqrt(sum deficit^2) | 9 first non-finite element (-1: none). 5..7 run over the finite ones. */
+/* out: [element][10] or NULL; spectrum: [element][3 NB] ascending (ties in index order) or NULL; both NULL: n_elem and nb alone, nothing is launched. */
+int mistark_potential_spectrum_report(mistark_ctx* ctx, int potential, int source, double eps, double* out, double* spectrum, int64_t* n_elem, int32_t* nb);
+/* out_host[block row][5] over the listed potentials. */
+int mistark_nodal_spectrum(mistark_ctx* ctx, const int32_t* potentials, int32_t n, int source, double eps, double* out_host);
+/* out[k][10] for the k-th listed potential; one without elements reports zeros with -1 in slots 6 and 9. */
+int mistark_spectrum_potential_report(mistark_ctx* ctx, const int32_t* potentials, int32_t n, int source, double eps, double* out);
+
 /* ---- rigid-body wrench report -------------------------------------------------------------------------------------------------
  * The free-body diagram of a rigid body: force and torque on it from any potential (rows) and from any family of potentials (bodies), at the current
  * DoFs. Every rigid potential places a body through t1 = t0 + dt v1 and the normalised quaternion q0 + dt/2 (0, w1) q0, that is R1 = C(a) R0 with C the
@@ -525,7 +554,9 @@ int mistark_sync(mistark_ctx* ctx);
  * (the same two for the friction report), "constraint_reports" / "constraint_report_chunks" (constraint report calls that launched, chunks the last group
  * report was summed in), "bending_reports" / "bending_report_long_rows" / "bending_report_chunks" (bending report calls that launched, block rows of the
  * last nodal stage summed by a whole wavefront, chunks the last group stage was summed in), "wrench_reports" / "wrench_long_rows" (wrench report calls
- * that launched, rigid-body block rows of the last body report summed by a whole wavefront, over all its families). */
+ * that launched, rigid-body block rows of the last body report summed by a whole wavefront, over all its families), "spectrum_reports" /
+ * "spectrum_report_long_rows" / "spectrum_report_chunks" (spectrum report calls that launched, block rows of the last nodal stage handled by a whole
+ * wavefront: more than 64 contributions, chunks the last potential stage was summed in). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

@@ -270,6 +270,19 @@ int mistark_sim_record_bending(mistark_sim* sim, int enabled, double threshold_r
 int mistark_sim_get_bending(mistark_sim* sim, int kind, int32_t* present, int64_t* n_rows, int32_t* n_groups, double* time, double* rows, double* groups);
 /* points_out [n_points x 6]: the nodal records of both kinds together. */
 int mistark_sim_get_nodal_bending(mistark_sim* sim, double* points_out);
+/* Spectrum recording (off by default; not in the reference), at the same place inside the step, after the Newton callbacks that precede an evaluation: one
+ * Hessian spectrum report (mistark.h "Hessian spectrum report", source 1: a fresh evaluation beside the solver's, nothing the solver owns is written) over
+ * every built-in potential of the scene: potential records of 10 doubles, nodal records of 5, element records of 10. eps is the threshold of the test
+ * `l < eps`; negative: the Newton settings' projection_eps at the time of the step; not finite: refused. Results stay on the device until they are asked
+ * for. With recording off nothing is launched or allocated and the step log and the trajectory are the same bits. */
+int mistark_sim_record_spectrum(mistark_sim* sim, int enabled, double eps);
+/* The report of the last accepted step. Every output is nullable; a first call with the buffers NULL gives the sizes and downloads nothing. names: the
+ * registry names of the recorded potentials in id order, each followed by a newline, names_bytes with the final 0; potentials [n_potentials x 10]. */
+int mistark_sim_get_spectrum(mistark_sim* sim, int32_t* n_potentials, int64_t* names_bytes, double* eps, double* time, double* potentials, char* names);
+/* points_out [n_points x 5]: the nodal records of the point set. */
+int mistark_sim_get_nodal_spectrum(mistark_sim* sim, double* points_out);
+/* rows [n_rows x 10] of the recorded potential of that registry name, fetched on demand; rows NULL: the count alone. capacity: rows the buffer holds. */
+int mistark_sim_get_spectrum_rows(mistark_sim* sim, const char* name, int64_t* n_rows, double* rows, int64_t capacity);
 /* Wrench recording (off by default; not in the reference), at the same place inside the step, after the Newton callbacks that precede an evaluation: one
  * body report (mistark.h "rigid-body wrench report": per family and body a record of 16 doubles and an element count) over seven fixed families of
  * potentials, in this order: linear inertia (EnergyRigidBodyInertia_Linear: with gravity and applied forces), angular inertia, the rb_constraint_* kinds,

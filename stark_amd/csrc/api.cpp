@@ -589,6 +589,9 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "bending_reports") *out = c.n_bending_reports;
     else if (n == "bending_report_long_rows") *out = bending_long_rows(c);
     else if (n == "bending_report_chunks") *out = c.n_bending_chunks;
+    else if (n == "spectrum_reports") *out = c.n_spectrum_reports;
+    else if (n == "spectrum_report_long_rows") *out = spectrum_long_rows(c);
+    else if (n == "spectrum_report_chunks") *out = c.n_spectrum_chunks;
     else if (n == "wrench_reports") *out = c.n_wrench_reports;
     else if (n == "wrench_long_rows") *out = wrench_long_rows(c);
     else if (n == "contact_reports") *out = c.n_contact_reports;
@@ -780,6 +783,27 @@ int mistark_bending_group_report(mistark_ctx* ctx, int potential, const double* 
 {
     API_BEGIN
     bending_groups_host(ctx->c, potential, threshold, n_groups, out);
+    API_END(0)
+}
+
+// ---- Hessian spectrum report (spectrum_report.hip) ---------------------------------------------------------------------------
+int mistark_potential_spectrum_report(mistark_ctx* ctx, int potential, int source, double eps, double* out, double* spectrum, int64_t* n_elem, int32_t* nb)
+{
+    API_BEGIN
+    if (potential < 0 || potential >= (int)ctx->c.pots.size()) throw Error("mistark_potential_spectrum_report: bad potential id " + std::to_string(potential));
+    spectrum_rows_host(ctx->c, potential, source, eps, out, spectrum, n_elem, nb);
+    API_END(0)
+}
+int mistark_nodal_spectrum(mistark_ctx* ctx, const int32_t* potentials, int32_t n, int source, double eps, double* out_host)
+{
+    API_BEGIN
+    spectrum_nodal_host(ctx->c, potentials, n, source, eps, out_host);
+    API_END(0)
+}
+int mistark_spectrum_potential_report(mistark_ctx* ctx, const int32_t* potentials, int32_t n, int source, double eps, double* out)
+{
+    API_BEGIN
+    spectrum_pots_host(ctx->c, potentials, n, source, eps, out);
     API_END(0)
 }
 
@@ -1620,6 +1644,24 @@ int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows)
 {
     API_BEGIN
     mistark::bending_fetch_nodal(ctx->c, out, n_rows);
+    API_END(0)
+}
+int spectrum_record(mistark_ctx* ctx, const std::vector<int32_t>& pots, double eps)
+{
+    API_BEGIN
+    spectrum_record_step(ctx->c, pots.data(), (int32_t)pots.size(), eps);
+    API_END(0)
+}
+int spectrum_fetch(mistark_ctx* ctx, int32_t n, double* pots_out, double* nodal_out, int64_t n_rows)
+{
+    API_BEGIN
+    spectrum_fetch_summary(ctx->c, n, pots_out, nodal_out, n_rows);
+    API_END(0)
+}
+int spectrum_fetch_rows(mistark_ctx* ctx, int32_t index, double* rows, int64_t* n_rows)
+{
+    API_BEGIN
+    mistark::spectrum_fetch_rows(ctx->c, index, rows, n_rows);
     API_END(0)
 }
 int wrench_record(mistark_ctx* ctx, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,

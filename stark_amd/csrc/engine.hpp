@@ -699,6 +699,30 @@ struct Context
     int32_t wr_out_families = 0, wr_out_bodies = 0;  // what wr_out / wr_count hold of the last body report
     int64_t n_wrench_reports = 0;      // counter "wrench_reports": calls that launched
 
+    // Hessian spectrum report (spectrum_report.hip): the ninth pipeline beside eval(). Element records field-major in spr_rec ([10][elements of the
+    // selection]), sorted eigenvalues spr_spec [element][3 NB] of a single potential; source 1 evaluates one potential at a time into spr_H
+    // ([NB^2][elements][3][3], sized by the largest: 72 NB^2 bytes per element) with spr_gpool / spr_elemE taking what the kernel emits beside;
+    // contributions (element, block) sorted by block row -> spr_nodal [nbr][5]; chunks of SPEC_CHUNK elements -> spr_partial [chunk][11] ->
+    // spr_pot [potential][10]. Nothing but these buffers is written.
+    DevBuf<double> spr_rec, spr_spec, spr_H, spr_gpool, spr_elemE, spr_nodal, spr_partial, spr_pot;
+    DevBuf<uint32_t> spr_key, spr_key_alt, spr_val, spr_val_alt;
+    DevBuf<uint32_t> spr_stat;         // [0]: rows of the last nodal stage handled by a whole wavefront (counter "spectrum_report_long_rows")
+    DevBuf<unsigned char> spr_desc, spr_sdesc;
+    DevBuf<uint8_t> spr_cub_tmp;
+    DevBuf<int32_t> spr_chunks;
+    struct SpectrumSlot                // what the host mirror records inside a time step and keeps on the device
+    {
+        DevBuf<double> rec, nodal, pot;
+        std::vector<int> slot_of;      // per listed potential: its index among those with elements, -1: none
+        std::vector<int64_t> col0, n_elem;  // per potential with elements: first column in rec, elements
+        int64_t N = -1;                // columns of rec (-1: nothing yet)
+        int64_t nbr = 0;
+    };
+    SpectrumSlot spr_slot;
+    int64_t n_spectrum_reports = 0;    // counter "spectrum_reports": calls that launched
+    int64_t n_spectrum_chunks = 0;     // counter "spectrum_report_chunks": chunks of the last potential stage
+    bool spr_stat_valid = false;
+
     int last_cg_iters = 0;         // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -879,6 +903,18 @@ int64_t bending_long_rows(Context& c);  // counter "bending_report_long_rows"
 void bending_record_step(Context& c, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups);  // into Context::bdr_slot; -1: not registered
 void bending_fetch_kind(Context& c, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups);
 void bending_fetch_nodal(Context& c, double* out, int64_t n_rows);
+// Hessian spectrum report (spectrum_report.hip, records as spectrum_report.hpp lays them out). source 0: the element-Hessian pool as it stands, 1: a fresh
+// evaluation at the current DoFs into a pool of the report's own. kernels.hip: the generic hyper-dual kernel of P's kind with Hessian blocks to `Hpool`
+// ([NB^2][n_elem][3][3]), node gradients to `scratch_gpool` ([NB][n_elem][3]) and energies to `scratchE`; nothing eval() owns is written.
+void launch_hessian_elements(Context& c, const Potential& P, double* Hpool, double* scratchE, double* scratch_gpool);
+void spectrum_rows_host(Context& c, int pot, int source, double eps, double* out, double* spectrum, int64_t* n_elem, int32_t* nb);
+void spectrum_nodal_host(Context& c, const int32_t* pots, int32_t n, int source, double eps, double* out_host);
+void spectrum_pots_host(Context& c, const int32_t* pots, int32_t n, int source, double eps, double* out);
+int64_t spectrum_long_rows(Context& c);  // counter "spectrum_report_long_rows"
+// the host mirror's recording inside a time step: source 1 over the listed potentials, element, nodal and potential records into Context::spr_slot
+void spectrum_record_step(Context& c, const int32_t* pots, int32_t n, double eps);
+void spectrum_fetch_summary(Context& c, int32_t n, double* pots_out, double* nodal_out, int64_t n_rows);  // [n][10] (n as recorded), [n_rows][5]; both nullable
+void spectrum_fetch_rows(Context& c, int32_t index, double* rows, int64_t* n_rows);  // [n_rows][10] of the index-th listed potential; rows nullable
 // Rigid-body wrench report (wrench.hip, records as wrench.hpp lays them out). v1, w1, t0, q0: array ids of the bodies' state. Null outputs are skipped.
 void wrench_rows_host(Context& c, int pot, int v1, int w1, int t0, int q0, int32_t n_bodies, double* out, int32_t* ids, int64_t* n_rows);
 void wrench_bodies_host(Context& c, const int32_t* families, const int32_t* family_start, int32_t n_families, int v1, int w1, int t0, int q0, int32_t n_bodies, const double* about,

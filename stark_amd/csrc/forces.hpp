@@ -36,6 +36,12 @@ int constraint_fetch(mistark_ctx* ctx, int kind, double* out, double* aux, int32
 int bending_record(mistark_ctx* ctx, int pot_complete, int pot_flat, const double* threshold, int32_t n_groups);
 int bending_fetch(mistark_ctx* ctx, int kind, double* rows, double* groups, int64_t* n_rows, int32_t* n_groups);
 int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows);
+// Hessian spectrum report (spectrum_report.hip), source 1 over the listed potentials: element, nodal and potential records into the device set of the host
+// mirror. Fetch: pots_out [n][10] for the n listed potentials, nodal_out [n_rows][5], n_rows = block rows of the DoF vector (both nullable); rows
+// [n_rows][10] of the index-th listed potential (rows nullable: the count alone)
+int spectrum_record(mistark_ctx* ctx, const std::vector<int32_t>& pots, double eps);
+int spectrum_fetch(mistark_ctx* ctx, int32_t n, double* pots_out, double* nodal_out, int64_t n_rows);
+int spectrum_fetch_rows(mistark_ctx* ctx, int32_t index, double* rows, int64_t* n_rows);
 // rigid-body wrench report (wrench.hip): the body report of the given families of potentials (an empty list: the zero wrench, unless all[f]: every
 // potential) kept on the device; out [n_families][n_bodies][16], count [n_families][n_bodies]
 int wrench_record(mistark_ctx* ctx, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,

@@ -62,6 +62,7 @@ void Stark::ensure_registered()
     constraint_sources.clear();
     bending_recorded = false;
     bending_source = BendingSource{};
+    spectrum_recorded = false;
     wrench_recorded = false;
     wrench_source = WrenchSource{};
     contact_labels = nullptr;
@@ -260,6 +261,23 @@ bool Stark::run_one_step()
             bending_recorded_source = src;
             bending_time = current_time + dt;
             bending_recorded = true;
+        }
+        if (spectrum_recording) {
+            for (auto& f : n.before_energy_evaluation) f();  // (as force recording: the installed contact tables are then this state's)
+            std::vector<std::string> names;
+            std::vector<char> custom;
+            check(potential_names(ctx, names, custom));
+            spectrum_pots.clear();
+            spectrum_names.clear();
+            for (size_t p = 0; p < names.size(); p++)
+                if (!custom[p]) {
+                    spectrum_pots.push_back((int32_t)p);
+                    spectrum_names.push_back(names[p]);
+                }
+            spectrum_eps_recorded = spectrum_eps >= 0.0 ? spectrum_eps : settings.newton.projection_eps;
+            check(spectrum_record(ctx, spectrum_pots, spectrum_eps_recorded));
+            spectrum_time = current_time + dt;
+            spectrum_recorded = true;
         }
         if (wrench_recording) {
             for (auto& f : n.before_energy_evaluation) f();  // (as force recording: the installed contact tables are then this state's)
@@ -479,6 +497,49 @@ void Stark::get_nodal_bending(double* points_out)
     const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
     if (r0 < 0) throw std::runtime_error("get_nodal_bending: the point set has no DoFs");
     std::copy(all.begin() + 6 * r0, all.begin() + 6 * (r0 + force_n_points), points_out);
+}
+void Stark::record_spectrum(bool enabled, double eps)
+{
+    if (std::isnan(eps) || std::isinf(eps)) throw std::runtime_error("record_spectrum: eps is not finite");
+    spectrum_recording = enabled;
+    spectrum_eps = eps;
+    spectrum_recorded = false;
+}
+void Stark::get_spectrum(SpectrumReport& out, bool sizes_only)
+{
+    if (!spectrum_recording) throw std::runtime_error("get_spectrum: spectrum recording is off (record_spectrum)");
+    if (!ctx || !spectrum_recorded) throw std::runtime_error("get_spectrum: no time step has been accepted since recording was switched on");
+    out = SpectrumReport{};
+    out.names = spectrum_names;
+    out.eps = spectrum_eps_recorded;
+    out.time = spectrum_time;
+    if (sizes_only) return;
+    out.potentials.resize((size_t)10 * spectrum_pots.size());
+    if (!spectrum_pots.empty()) check(spectrum_fetch(ctx, (int32_t)spectrum_pots.size(), out.potentials.data(), nullptr, 0));
+}
+void Stark::get_nodal_spectrum(double* points_out)
+{
+    if (!spectrum_recording) throw std::runtime_error("get_nodal_spectrum: spectrum recording is off (record_spectrum)");
+    if (!ctx || !spectrum_recorded) throw std::runtime_error("get_nodal_spectrum: no time step has been accepted since recording was switched on");
+    if (!points_out || force_n_points <= 0) return;
+    const int64_t nbr = mistark_ndofs(ctx) / 3;
+    std::vector<double> all((size_t)nbr * 5);
+    check(spectrum_fetch(ctx, 0, nullptr, all.data(), nbr));
+    const int64_t r0 = mistark_dof_set_first_row(ctx, force_set_points);
+    if (r0 < 0) throw std::runtime_error("get_nodal_spectrum: the point set has no DoFs");
+    std::copy(all.begin() + 5 * r0, all.begin() + 5 * (r0 + force_n_points), points_out);
+}
+void Stark::get_spectrum_rows(const std::string& name, std::vector<double>& rows)
+{
+    if (!spectrum_recording) throw std::runtime_error("get_spectrum_rows: spectrum recording is off (record_spectrum)");
+    if (!ctx || !spectrum_recorded) throw std::runtime_error("get_spectrum_rows: no time step has been accepted since recording was switched on");
+    size_t k = 0;
+    while (k < spectrum_names.size() && spectrum_names[k] != name) k++;
+    if (k == spectrum_names.size()) throw std::runtime_error("get_spectrum_rows: no recorded potential '" + name + "'");
+    int64_t n = 0;
+    check(spectrum_fetch_rows(ctx, (int32_t)k, nullptr, &n));
+    rows.assign((size_t)10 * n, 0.0);
+    if (n > 0) check(spectrum_fetch_rows(ctx, (int32_t)k, rows.data(), nullptr));
 }
 void Stark::record_wrench(bool enabled, const Vec3& about)
 {

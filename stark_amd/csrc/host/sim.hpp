@@ -265,6 +265,21 @@ public:
         int32_t n_groups = 0;
     };
     BendingSource bending_source;
+    // Spectrum recording (off by default; not in the reference): at the same place, after the before_energy_evaluation callbacks, one Hessian spectrum report
+    // (include/mistark.h "Hessian spectrum report", source 1: a fresh evaluation beside the solver's) over every built-in potential: potential records,
+    // nodal records and element records, kept on the device until get_spectrum() / get_nodal_spectrum() / get_spectrum_rows() download them. eps: the
+    // threshold of the test `l < eps`; negative: the Newton settings' projection_eps at the time of the step. Off: nothing is launched or allocated.
+    struct SpectrumReport
+    {
+        std::vector<std::string> names;   // registry names of the recorded potentials, in id order
+        std::vector<double> potentials;   // [names.size()][10]
+        double eps = 0.0, time = 0.0;     // as recorded; simulation time of the accepted step
+    };
+    void record_spectrum(bool enabled, double eps = -1.0);
+    void get_spectrum(SpectrumReport& out, bool sizes_only = false);  // sizes_only: names, eps and time; nothing is downloaded
+    void get_nodal_spectrum(double* points_out /* n_points x 5 */);
+    void get_spectrum_rows(const std::string& name, std::vector<double>& rows /* [n_elem][10] */);
+    bool spectrum_recording = false, spectrum_recorded = false;
     // Wrench recording (off by default; not in the reference): at the same place, after the before_energy_evaluation callbacks, one body report of the
     // rigid-body wrench report (include/mistark.h "rigid-body wrench report": per family and body a record of 16 doubles and an element count) over
     // seven fixed families of potentials, kept on the device until get_wrench() downloads it. Off: nothing is launched or allocated. A scene without
@@ -311,6 +326,9 @@ private:
     double budget_time = 0.0, contacts_time = 0.0, friction_time = 0.0, constraints_time = 0.0;
     Vec3 constraint_about = {0.0, 0.0, 0.0};
     double bending_threshold = 0.0, bending_time = 0.0;
+    double spectrum_eps = -1.0, spectrum_eps_recorded = 0.0, spectrum_time = 0.0;
+    std::vector<int32_t> spectrum_pots;        // the potentials of the report recorded at the last accepted step
+    std::vector<std::string> spectrum_names;
     Vec3 wrench_about = {0.0, 0.0, 0.0};
     double wrench_time = 0.0;
     int32_t wrench_bodies = 0;  // bodies of the report recorded at the last accepted step

@@ -924,6 +924,45 @@ int mistark_sim_get_nodal_bending(mistark_sim* s, double* points_out)
     s->sim->get_stark().get_nodal_bending(points_out);
     SIM_END
 }
+int mistark_sim_record_spectrum(mistark_sim* s, int enabled, double eps)
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_spectrum(enabled != 0, eps);
+    SIM_END
+}
+int mistark_sim_get_spectrum(mistark_sim* s, int32_t* n_potentials, int64_t* names_bytes, double* eps, double* time, double* potentials, char* names)
+{
+    SIM_BEGIN
+    Stark::SpectrumReport r;
+    s->sim->get_stark().get_spectrum(r, !potentials);  // (the size query downloads nothing)
+    std::string nm;
+    for (const auto& l : r.names) nm += l + "\n";
+    if (n_potentials) *n_potentials = (int32_t)r.names.size();
+    if (names_bytes) *names_bytes = (int64_t)nm.size() + 1;
+    if (eps) *eps = r.eps;
+    if (time) *time = r.time;
+    if (potentials) std::copy(r.potentials.begin(), r.potentials.end(), potentials);
+    if (names) std::memcpy(names, nm.c_str(), nm.size() + 1);
+    SIM_END
+}
+int mistark_sim_get_nodal_spectrum(mistark_sim* s, double* points_out)
+{
+    SIM_BEGIN
+    s->sim->get_stark().get_nodal_spectrum(points_out);
+    SIM_END
+}
+int mistark_sim_get_spectrum_rows(mistark_sim* s, const char* name, int64_t* n_rows, double* rows, int64_t capacity)
+{
+    SIM_BEGIN
+    std::vector<double> r;
+    s->sim->get_stark().get_spectrum_rows(name ? name : "", r);
+    if (n_rows) *n_rows = (int64_t)r.size() / 10;
+    if (rows) {
+        if (capacity < (int64_t)r.size() / 10) throw std::runtime_error("mistark_sim_get_spectrum_rows: the buffer holds fewer rows than the potential has");
+        std::copy(r.begin(), r.end(), rows);
+    }
+    SIM_END
+}
 int mistark_sim_record_wrench(mistark_sim* s, int enabled, const double about[3])
 {
     SIM_BEGIN

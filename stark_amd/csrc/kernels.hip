@@ -897,6 +897,32 @@ void launch_force_elements(Context& c, const Potential& P, double* pool, double*
     throw Error("unknown potential kind");
 }
 
+// Spectrum report (spectrum_report.hip), source 1: the generic kernel on a copy of the potential's argument block — Hessian blocks to the report's pool
+// (n_pool = n_elem), node gradients to a scratch pool, element energies to a scratch array, no gradient vector. Nothing eval() owns is written.
+template <class En>
+static void launch_hessian_kind(Context& c, const Potential& P, double* Hpool, double* scratchE, double* scratch_gpool)
+{
+    constexpr int n = 3 * En::NB, NP = n * (n + 1) / 2;
+    PotArgs A = P.args;
+    A.gpool = scratch_gpool;
+    A.n_gpool = P.n_elem;
+    A.n_pool = P.n_elem;
+    hipLaunchKernelGGL((k_eval_pgh<En, true>), dim3(grid_for((int64_t)A.e_count * NP)), dim3(BLOCK), 0, c.stream, A, scratchE, Hpool, (double*)nullptr);
+}
+void launch_hessian_elements(Context& c, const Potential& P, double* Hpool, double* scratchE, double* scratch_gpool)
+{
+    if (P.kind == KIND_CUSTOM) throw Error("spectrum report: potential '" + P.name + "' is user-defined (its kernels have no pool path)");
+    if (P.args.e_count == 0) return;
+    if (P.args.elem_list || P.args.e_count != P.n_elem) throw Error("spectrum report: single-rank accessor");
+    int k = 0;
+#define X(En)                                                                                \
+    if (P.kind == k) { launch_hessian_kind<En>(c, P, Hpool, scratchE, scratch_gpool); return; } \
+    k++;
+    MISTARK_FOR_EACH_ENERGY(X)
+#undef X
+    throw Error("unknown potential kind");
+}
+
 // Budget readout (budget.hip): the energy-only kernel on a copy of the potential's argument block, element energies to `scratchE` (zeros for
 // elements switched off). Nothing eval() owns is written.
 void launch_energy_elements(Context& c, const Potential& P, double* scratchE)

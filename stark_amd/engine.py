@@ -514,6 +514,35 @@ class Engine:
         self._ck(self.L.mistark_bending_group_report(self.h, int(pot), tp, ng, out.ctypes.data if out.size else None))
         return out
 
+    # ---- Hessian spectrum report (include/mistark.h "Hessian spectrum report") ------------------------------------------------
+    def spectrum_report(self, pot: int, source: int = 0, eps: float = 1e-10, spectrum: bool = False) -> dict:
+        """The element records of one potential's Hessian spectra, columns named (spectrum_rows_dict). source 0: the element Hessians as they stand
+        after eval(P_G_H) / project(); 1: a fresh evaluation at the current DoFs beside eval(). spectrum=True adds the sorted eigenvalues [n_elem, 3 NB]."""
+        n, nb = C.c_int64(), C.c_int32()
+        self._ck(self.L.mistark_potential_spectrum_report(self.h, int(pot), int(source), float(eps), None, None, C.byref(n), C.byref(nb)))
+        rec = np.zeros((n.value, 10))
+        spec = np.zeros((n.value, 3 * nb.value)) if spectrum else None
+        if n.value:
+            self._ck(self.L.mistark_potential_spectrum_report(self.h, int(pot), int(source), float(eps), rec.ctypes.data, spec.ctypes.data if spectrum else None,
+                                                               C.byref(n), C.byref(nb)))
+        return spectrum_rows_dict(rec, nb.value, spec)
+
+    def nodal_spectrum(self, pots, source: int = 0, eps: float = 1e-10) -> np.ndarray:
+        """out[block rows, 5] over the listed potentials: elements touching the row, of them flagged (the projection would change them), smallest
+        lambda_min among them, sum of deficit^2, potential id holding the smallest (-1: none)."""
+        ids, ptr = self._pot_list(pots)
+        out = np.zeros((self.ndofs // 3, 5))
+        self._ck(self.L.mistark_nodal_spectrum(self.h, ptr, ids.size, int(source), float(eps), out.ctypes.data))
+        return out
+
+    def spectrum_potential_report(self, pots, source: int = 0, eps: float = 1e-10) -> np.ndarray:
+        """records [len(pots), 10]: elements, flagged, with lambda_min < 0, non-finite, not converged, smallest lambda_min, first element attaining it
+        (-1: none), largest lambda_max, sqrt(sum deficit^2), first non-finite element (-1: none)."""
+        ids, ptr = self._pot_list(pots)
+        out = np.zeros((ids.size, 10))
+        self._ck(self.L.mistark_spectrum_potential_report(self.h, ptr, ids.size, int(source), float(eps), out.ctypes.data if out.size else None))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)
@@ -631,6 +660,14 @@ def bending_rows_dict(rec, kind):
     return dict(records=rec, kind=int(kind), name=BENDING_KINDS[kind] if 0 <= kind < 2 else None, theta=rec[:, 0], phi=rec[:, 1], rest_angle=rec[:, 2], rate=rec[:, 3],
                 length=rec[:, 4], area=rec[:, 5], kappa=rec[:, 6], kappa_rest=rec[:, 7], moment=rec[:, 8], E_elastic=rec[:, 9], E_damping=rec[:, 10], normal=rec[:, 11:14],
                 group=rec[:, 14].astype(np.int64), flags=flags, degenerate=(flags & 1) != 0, beyond_threshold=(flags & 2) != 0)
+
+
+def spectrum_rows_dict(rec, nb, spectrum=None):
+    """The element array of a spectrum report with its columns named (views; counts and flags as integers)."""
+    flags = rec[:, 9].astype(np.int64)
+    return dict(records=rec, nb=int(nb), lambda_min=rec[:, 0], lambda_max=rec[:, 1], n_below_eps=rec[:, 2].astype(np.int64), n_negative=rec[:, 3].astype(np.int64),
+                deficit=rec[:, 4], frobenius=rec[:, 5], trace=rec[:, 6], sweeps=rec[:, 7].astype(np.int64), off=rec[:, 8], flags=flags, projected=(flags & 1) != 0,
+                non_finite=(flags & 2) != 0, not_converged=(flags & 4) != 0, spectrum=spectrum)
 
 
 def contact_vertices_dict(rec, group, source_index):

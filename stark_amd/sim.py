@@ -148,6 +148,10 @@ def _lib():
         L.mistark_sim_record_bending.argtypes = [p, C.c_int, C.c_double]
         L.mistark_sim_get_bending.argtypes = [p, C.c_int, I32, I64, I32, D, p, p]
         L.mistark_sim_get_nodal_bending.argtypes = [p, p]
+        L.mistark_sim_record_spectrum.argtypes = [p, C.c_int, C.c_double]
+        L.mistark_sim_get_spectrum.argtypes = [p, I32, I64, D, D, p, p]
+        L.mistark_sim_get_nodal_spectrum.argtypes = [p, p]
+        L.mistark_sim_get_spectrum_rows.argtypes = [p, C.c_char_p, I64, p, C.c_int64]
         L.mistark_sim_record_wrench.argtypes = [p, C.c_int, p]
         L.mistark_sim_wrench_sources.argtypes = [p, p, p, p]
         L.mistark_sim_get_wrench.argtypes = [p, I32, I32, I64, D, p, p, p]
@@ -630,6 +634,35 @@ class Simulation:
         if nodal.size:
             self._ck(self.L.mistark_sim_get_nodal_bending(self.h, nodal.ctypes.data))
         return dict(kinds=kinds, nodal=nodal, time=time)
+
+    # ---- spectrum recording ----------------------------------------------------------------------------------------------------
+    def record_spectrum(self, enabled=True, eps=None):
+        """Every accepted step then keeps the Hessian spectrum report of the state it converged at on the device: a fresh evaluation (source 1) over every
+        built-in potential, with potential, nodal and element records. eps: the threshold of `l < eps`; None: the Newton settings' projection eps."""
+        self._ck(self.L.mistark_sim_record_spectrum(self.h, int(bool(enabled)), -1.0 if eps is None else float(eps)))
+
+    def spectrum(self):
+        """The spectrum report of the last accepted step: dict(time, eps, names (registry names of the potentials, id order), potentials [n, 10] as
+        Engine.spectrum_potential_report() gives them, nodal [n_points, 5] for the point set). Raises while recording is off."""
+        n, nb, eps, t = C.c_int32(), C.c_int64(), C.c_double(), C.c_double()
+        self._ck(self.L.mistark_sim_get_spectrum(self.h, C.byref(n), C.byref(nb), C.byref(eps), C.byref(t), None, None))
+        pots = np.zeros((n.value, 10))
+        buf = C.create_string_buffer(max(int(nb.value), 1))
+        self._ck(self.L.mistark_sim_get_spectrum(self.h, C.byref(n), C.byref(nb), C.byref(eps), C.byref(t), pots.ctypes.data if pots.size else None, buf))
+        nodal = np.zeros((self.info().n_points, 5))
+        if nodal.size:
+            self._ck(self.L.mistark_sim_get_nodal_spectrum(self.h, nodal.ctypes.data))
+        return dict(time=t.value, eps=eps.value, names=buf.value.decode().split("\n")[:n.value], potentials=pots, nodal=nodal)
+
+    def spectrum_rows(self, name):
+        """The element records of one recorded potential (by registry name), fetched on demand: Engine.spectrum_report()'s dict without the spectrum."""
+        from .engine import spectrum_rows_dict
+        n = C.c_int64()
+        self._ck(self.L.mistark_sim_get_spectrum_rows(self.h, name.encode(), C.byref(n), None, 0))
+        rec = np.zeros((n.value, 10))
+        if n.value:
+            self._ck(self.L.mistark_sim_get_spectrum_rows(self.h, name.encode(), C.byref(n), rec.ctypes.data, n.value))
+        return spectrum_rows_dict(rec, 0)
 
     # ---- wrench recording ------------------------------------------------------------------------------------------------------
     WRENCH_FAMILIES = ("inertia_linear", "inertia_angular", "constraints", "attachments", "contact", "friction", "all")
