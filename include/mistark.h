@@ -302,6 +302,52 @@ int mistark_nodal_spectrum(mistark_ctx* ctx, const int32_t* potentials, int32_t 
 /* out[k][10] for the k-th listed potential; one without elements reports zeros with -1 in slots 6 and 9. */
 int mistark_spectrum_potential_report(mistark_ctx* ctx, const int32_t* potentials, int32_t n, int source, double eps, double* out);
 
+/* ---- linear-system report ---------------------------------------------------------------------------------------------------------
+ * What the linear solver is given: the spectrum of the assembled matrix as it stands (the state after mistark_assemble, the static and the dynamic part
+ * together), its conditioning, the extreme modes and who carries them. Lanczos with full reorthogonalisation (two passes of classical Gram-Schmidt per
+ * step) in double on the device; a pipeline of its own beside mistark_eval and mistark_pcg, read-only on what the solver owns, without floating-point
+ * atomics, bit-reproducible, and nothing is launched unless it is called. Each call is a fresh, deterministic run; no state is kept between calls.
+ * Operators: MISTARK_LINSYS_A, B = A; MISTARK_LINSYS_JACOBI, B = L^-1 A L^-T with L block diagonal and L_r L_r^T = D_r the 3x3 Cholesky in double of the
+ *   row's stored float diagonal block. The eigenvalues of B are those of A x = lambda D x, the spectrum the block-Jacobi PCG works on. PCG itself applies
+ *   the inverse of D_r computed and stored in float; the two differ by the rounding of that inverse. If any D_r has a pivot <= 0 nothing is iterated and the
+ *   record says so (flag +8, slots 11..14): a finding in itself.
+ * Iteration j = 0 .. m-1, 1 <= m <= 256: w = B v_j; alpha_j = v_j . w; w -= alpha_j v_j + beta_{j-1} v_{j-1}; two Gram-Schmidt passes against v_0 .. v_j;
+ *   beta_j = |w|; T_norm = max_j (|alpha_j| + beta_j + beta_{j-1}). It stops after step j when beta_j <= 1e-10 T_norm (flag +1), j + 1 == m or j + 1 == n;
+ *   otherwise v_{j+1} = w / beta_j. With k steps run, T is the k x k tridiagonal matrix, (theta_i, s_i) its eigenpairs (a symmetric QL solver of the
+ *   library's own, in double on the host) and rho_i = beta_{k-1} |s_i[k-1]| the residual bound of Ritz value i: in exact arithmetic some eigenvalue of B
+ *   lies within rho_i of theta_i.
+ * start_host NULL: the built-in vector, in DoF order (the order mistark_spmv takes its host vectors in) entry i from z = (i+1) * 0x9E3779B97F4A7C15,
+ *   z = (z ^ z>>30) * 0xBF58476D1CE4E5B9, z = (z ^ z>>27) * 0x94D049BB133111EB, z ^= z>>31 in uint64, value (z >> 11) * 2^-52 - 1, then normalised.
+ *   Otherwise the caller's ndofs doubles (minus the gradient of the last evaluation gives the Ritz values PCG from x0 = 0 meets). A zero or non-finite
+ *   start vector is refused.
+ * Summary record, 16 doubles: 0 steps run k | 1 flags | 2 theta_min | 3 its rho | 4 theta_max | 5 its rho | 6 theta_max / theta_min, 0 where theta_min <= 0
+ *   | 7 T_norm | 8 beta_{k-1} | 9 Ritz values < 0 | 10 Ritz values with rho_i <= 1e-8 T_norm | 11 diagonal blocks that are not positive definite | 12 the
+ *   first such block row, or -1 | 13 smallest squared Cholesky pivot over all rows | 14 its row | 15 n. Slots 11..14 are filled for both operators.
+ *   Flags: +1 Krylov space exhausted | +2 theta_min < -64 eps T_norm (Ritz values lie inside the spectrum's range, so the matrix is proved indefinite) | +4 a
+ *   non-finite value was met, slots 2..10 are zeros | +8 operator 1 refused for a diagonal block that is not PD, slots 0 and 2..10 are zeros.
+ * Mode record, 4 doubles: 0 theta | 1 rho | 2 |B u - theta u| measured by one more operator application, a true a-posteriori residual, not the recurrence's
+ *   | 3 the index in the ascending list.
+ * Nodal record, 4 doubles per block row: 0 |u_r|^2, the row's share of the unit Ritz vector u = V s (the shares sum to 1) | 1 |x_r| | 2 trace of D_r | 3
+ *   smallest squared pivot of D_r.
+ * Potential record, 4 doubles: 0 sum q_e, summed in element order | 1 sum |q_e| | 2 elements that contribute: a stored entry of H_e is not zero (an element
+ *   whose condition is off stores zeros) | 3 first element attaining the largest |q_e|, or -1; q_e = x_e^T H_e x_e over the element-Hessian pool as it
+ *   stands, x the Ritz vector in DoF space. Over all potentials slot 0 adds up to x^T A x, which is theta under the normalisation below. Refused as source 0
+ *   of the spectrum report is: no Hessians evaluated, the float blocks of the lazy path. User-defined potentials are allowed.
+ * Refused with an error: registration-only contexts, sharded contexts, no assembled matrix, m out of range, a bad operator, a bad which, bad or duplicate
+ *   potential ids. When every output pointer is NULL nothing is launched. */
+enum { MISTARK_LINSYS_A = 0, MISTARK_LINSYS_JACOBI = 1 };
+/* out[16]; ritz[m][2] = theta ascending, rho (rows >= k zero) or NULL; tri[m][2] = alpha_j, beta_j or NULL; k_out: steps run */
+int mistark_linsys_report(mistark_ctx* ctx, int op, int m, const double* start_host, double* out, double* ritz, double* tri, int32_t* k_out);
+/* which[i] >= 0: i-th smallest Ritz value; < 0: counted from the largest (-1 = largest).
+   x_host[n_which][ndofs] or NULL: x with x^T D x = 1 (op 1) or |x| = 1 (op 0), DoF order.
+   nodal[n_which][block rows][4] or NULL.  mode[n_which][4]. */
+int mistark_linsys_modes(mistark_ctx* ctx, int op, int m, const double* start_host, const int32_t* which, int32_t n_which, double* x_host, double* nodal, double* mode);
+/* rhs_host[ndofs]: minus the gradient of the last evaluation in DoF order, the right-hand side mistark_pcg solves for; as start_host it gives the Ritz
+   values PCG from x0 = 0 meets. Single-rank accessor. */
+int mistark_linsys_rhs(mistark_ctx* ctx, double* rhs_host);
+/* out[n][4] for the n listed potentials, for one Ritz vector */
+int mistark_linsys_potential_shares(mistark_ctx* ctx, int op, int m, const double* start_host, int32_t which, const int32_t* potentials, int32_t n, double* out);
+
 /* ---- rigid-body wrench report -------------------------------------------------------------------------------------------------
  * The free-body diagram of a rigid body: force and torque on it from any potential (rows) and from any family of potentials (bodies), at the current
  * DoFs. Every rigid potential places a body through t1 = t0 + dt v1 and the normalised quaternion q0 + dt/2 (0, w1) q0, that is R1 = C(a) R0 with C the
@@ -556,7 +602,7 @@ int mistark_sync(mistark_ctx* ctx);
  * last nodal stage summed by a whole wavefront, chunks the last group stage was summed in), "wrench_reports" / "wrench_long_rows" (wrench report calls
  * that launched, rigid-body block rows of the last body report summed by a whole wavefront, over all its families), "spectrum_reports" /
  * "spectrum_report_long_rows" / "spectrum_report_chunks" (spectrum report calls that launched, block rows of the last nodal stage handled by a whole
- * wavefront: more than 64 contributions, chunks the last potential stage was summed in). */
+ * wavefront: more than 64 contributions, chunks the last potential stage was summed in), "linsys_reports" (linear-system report calls that launched). */
 int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- multi-GPU: one problem sharded over `world` ranks, one engine context (and one process) per GPU ------------------------

@@ -283,6 +283,14 @@ int mistark_sim_get_spectrum(mistark_sim* sim, int32_t* n_potentials, int64_t* n
 int mistark_sim_get_nodal_spectrum(mistark_sim* sim, double* points_out);
 /* rows [n_rows x 10] of the recorded potential of that registry name, fetched on demand; rows NULL: the count alone. capacity: rows the buffer holds. */
 int mistark_sim_get_spectrum_rows(mistark_sim* sim, const char* name, int64_t* n_rows, double* rows, int64_t capacity);
+/* Linear-system recording (off by default; not in the reference): right after a time step is accepted, before any other recording, one linear-system
+ * report (mistark.h "linear-system report", built-in start vector, operator op, at most m steps) of the matrix as the step's last assembly left it. Refused
+ * with an error when the step left no assembled matrix, for an operator other than 0 / 1 and for m outside 1..256. With recording off nothing is launched
+ * or allocated and the step log and the trajectory are the same bits. */
+int mistark_sim_record_linsys(mistark_sim* sim, int enabled, int op, int m);
+/* The report of the last accepted step. record [16]: the summary record; rows [4]: the block row with the largest share of the lowest mode, its share, the
+ * same for the highest mode (-1 and 0 where the run gave no Ritz pairs). Every output is nullable. */
+int mistark_sim_get_linsys(mistark_sim* sim, int32_t* op, int32_t* m, double* time, double* record, double* rows);
 /* Wrench recording (off by default; not in the reference), at the same place inside the step, after the Newton callbacks that precede an evaluation: one
  * body report (mistark.h "rigid-body wrench report": per family and body a record of 16 doubles and an element count) over seven fixed families of
  * potentials, in this order: linear inertia (EnergyRigidBodyInertia_Linear: with gravity and applied forces), angular inertia, the rb_constraint_* kinds,

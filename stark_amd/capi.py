@@ -135,6 +135,10 @@ def lib():
     L.mistark_potential_spectrum_report.argtypes = [p, C.c_int, C.c_int, dbl, p, p, C.POINTER(i64), C.POINTER(i32)]
     L.mistark_nodal_spectrum.argtypes = [p, p, i32, C.c_int, dbl, p]
     L.mistark_spectrum_potential_report.argtypes = [p, p, i32, C.c_int, dbl, p]
+    L.mistark_linsys_report.argtypes = [p, C.c_int, C.c_int, p, p, p, p, C.POINTER(i32)]
+    L.mistark_linsys_modes.argtypes = [p, C.c_int, C.c_int, p, p, i32, p, p, p]
+    L.mistark_linsys_potential_shares.argtypes = [p, C.c_int, C.c_int, p, i32, p, i32, p]
+    L.mistark_linsys_rhs.argtypes = [p, p]
     L.mistark_potential_rigid_wrench.argtypes =[p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32, p, p, C.POINTER(i64)]
     L.mistark_rigid_wrench.argtypes = [p, p, p, i32, C.c_int, C.c_int, C.c_int, C.c_int, i32, p, p, p]
     L.mistark_project.argtypes = [p, dbl, C.c_int, p, C.POINTER(i64), C.POINTER(i64)]

@@ -592,6 +592,7 @@ int mistark_get_counter(mistark_ctx* ctx, const char* name, int64_t* out)
     else if (n == "spectrum_reports") *out = c.n_spectrum_reports;
     else if (n == "spectrum_report_long_rows") *out = spectrum_long_rows(c);
     else if (n == "spectrum_report_chunks") *out = c.n_spectrum_chunks;
+    else if (n == "linsys_reports") *out = c.n_linsys_reports;
     else if (n == "wrench_reports") *out = c.n_wrench_reports;
     else if (n == "wrench_long_rows") *out = wrench_long_rows(c);
     else if (n == "contact_reports") *out = c.n_contact_reports;
@@ -804,6 +805,38 @@ int mistark_spectrum_potential_report(mistark_ctx* ctx, const int32_t* potential
 {
     API_BEGIN
     spectrum_pots_host(ctx->c, potentials, n, source, eps, out);
+    API_END(0)
+}
+
+// ---- linear-system report (linsys_report.hip) ----------------------------------------------------------------------------------
+int mistark_linsys_report(mistark_ctx* ctx, int op, int m, const double* start_host, double* out, double* ritz, double* tri, int32_t* k_out)
+{
+    API_BEGIN
+    linsys_report_host(ctx->c, op, m, start_host, out, ritz, tri, k_out);
+    API_END(0)
+}
+int mistark_linsys_modes(mistark_ctx* ctx, int op, int m, const double* start_host, const int32_t* which, int32_t n_which, double* x_host, double* nodal, double* mode)
+{
+    API_BEGIN
+    linsys_modes_host(ctx->c, op, m, start_host, which, n_which, x_host, nodal, mode);
+    API_END(0)
+}
+int mistark_linsys_rhs(mistark_ctx* ctx, double* rhs_host)
+{
+    API_BEGIN
+    Context& c = ctx->c;
+    if (c.dry) throw Error("mistark_linsys_rhs: registration-only context (mistark_create_dry): nothing can be evaluated");
+    if (c.world > 1) throw Error("mistark_linsys_rhs: single-rank accessor");
+    if (!rhs_host) throw Error("mistark_linsys_rhs: null output");
+    if (!c.grad.p || c.ndofs <= 0) throw Error("mistark_linsys_rhs: no gradient (call mistark_eval first)");
+    fetch(c, rhs_host, c.grad.p, (size_t)c.ndofs * sizeof(double));
+    for (int64_t i = 0; i < c.ndofs; i++) rhs_host[i] = -rhs_host[i];
+    API_END(0)
+}
+int mistark_linsys_potential_shares(mistark_ctx* ctx, int op, int m, const double* start_host, int32_t which, const int32_t* potentials, int32_t n, double* out)
+{
+    API_BEGIN
+    linsys_potential_shares_host(ctx->c, op, m, start_host, which, potentials, n, out);
     API_END(0)
 }
 
@@ -1662,6 +1695,18 @@ int spectrum_fetch_rows(mistark_ctx* ctx, int32_t index, double* rows, int64_t* 
 {
     API_BEGIN
     mistark::spectrum_fetch_rows(ctx->c, index, rows, n_rows);
+    API_END(0)
+}
+int linsys_record(mistark_ctx* ctx, int op, int m)
+{
+    API_BEGIN
+    linsys_record_step(ctx->c, op, m);
+    API_END(0)
+}
+int linsys_fetch(mistark_ctx* ctx, double* rec16, double* rows4)
+{
+    API_BEGIN
+    mistark::linsys_fetch(ctx->c, rec16, rows4);
     API_END(0)
 }
 int wrench_record(mistark_ctx* ctx, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,

@@ -723,6 +723,22 @@ struct Context
     int64_t n_spectrum_chunks = 0;     // counter "spectrum_report_chunks": chunks of the last potential stage
     bool spr_stat_valid = false;
 
+    // linear-system report (linsys_report.hip): the tenth pipeline, beside eval() and pcg(). Basis lsr_V [(m + 1)][even(n)], the iteration's vectors
+    // lsr_w / lsr_t / lsr_y, per-workgroup partial dots lsr_part [i][workgroup], coefficients lsr_c, the device control block lsr_ctrl (LsrCtrl), the
+    // Cholesky factors of the diagonal blocks lsr_L [solver row][6], trace and smallest pivot lsr_diag [block row][2], nodal records lsr_nodal, element
+    // quadratic forms lsr_q / lsr_nz of one potential. Allocated on first use, grown as needed, freed with the context; nothing else is written.
+    DevBuf<double> lsr_V, lsr_w, lsr_t, lsr_y, lsr_part, lsr_c, lsr_ctrl, lsr_L, lsr_diag, lsr_nodal, lsr_q;
+    DevBuf<uint8_t> lsr_nz;
+    DevBuf<int32_t> lsr_cols;
+    int64_t n_linsys_reports = 0;      // counter "linsys_reports": calls that launched
+    struct LinsysSlot                  // what the host mirror recorded of the last accepted step
+    {
+        bool valid = false;
+        double rec[16] = {0};
+        double low_row = -1.0, low_share = 0.0, high_row = -1.0, high_share = 0.0;
+    };
+    LinsysSlot lsr_slot;
+
     int last_cg_iters = 0;         // iteration count of the previous solve (first-batch predictor)
     // statistics of the last evaluation
     int64_t n_projected_total = 0;
@@ -915,6 +931,14 @@ int64_t spectrum_long_rows(Context& c);  // counter "spectrum_report_long_rows"
 void spectrum_record_step(Context& c, const int32_t* pots, int32_t n, double eps);
 void spectrum_fetch_summary(Context& c, int32_t n, double* pots_out, double* nodal_out, int64_t n_rows);  // [n][10] (n as recorded), [n_rows][5]; both nullable
 void spectrum_fetch_rows(Context& c, int32_t index, double* rows, int64_t* n_rows);  // [n_rows][10] of the index-th listed potential; rows nullable
+// Linear-system report (linsys_report.hip, records as linsys_report.hpp lays them out): Lanczos with full reorthogonalisation on the assembled matrix.
+// Each call is a fresh run; null outputs are skipped and a call whose outputs are all null launches nothing.
+void linsys_report_host(Context& c, int op, int m, const double* start_host, double* out, double* ritz, double* tri, int32_t* k_out);
+void linsys_modes_host(Context& c, int op, int m, const double* start_host, const int32_t* which, int32_t n_which, double* x_host, double* nodal, double* mode);
+void linsys_potential_shares_host(Context& c, int op, int m, const double* start_host, int32_t which, const int32_t* pots, int32_t n, double* out);
+// the host mirror's recording after an accepted time step: the summary record and the block rows with the largest share of the lowest and the highest mode
+void linsys_record_step(Context& c, int op, int m);
+void linsys_fetch(Context& c, double* rec16, double* rows4);  // rows4: low row, its share, high row, its share
 // Rigid-body wrench report (wrench.hip, records as wrench.hpp lays them out). v1, w1, t0, q0: array ids of the bodies' state. Null outputs are skipped.
 void wrench_rows_host(Context& c, int pot, int v1, int w1, int t0, int q0, int32_t n_bodies, double* out, int32_t* ids, int64_t* n_rows);
 void wrench_bodies_host(Context& c, const int32_t* families, const int32_t* family_start, int32_t n_families, int v1, int w1, int t0, int q0, int32_t n_bodies, const double* about,

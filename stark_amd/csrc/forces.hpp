@@ -42,6 +42,10 @@ int bending_fetch_nodal(mistark_ctx* ctx, double* out, int64_t n_rows);
 int spectrum_record(mistark_ctx* ctx, const std::vector<int32_t>& pots, double eps);
 int spectrum_fetch(mistark_ctx* ctx, int32_t n, double* pots_out, double* nodal_out, int64_t n_rows);
 int spectrum_fetch_rows(mistark_ctx* ctx, int32_t index, double* rows, int64_t* n_rows);
+// linear-system report (linsys_report.hip) of the matrix as the step's last assembly left it: the summary record and the block rows with the largest share
+// of the lowest and of the highest mode, kept in the context until fetched. rec16 [16]; rows4: low row, its share, high row, its share
+int linsys_record(mistark_ctx* ctx, int op, int m);
+int linsys_fetch(mistark_ctx* ctx, double* rec16, double* rows4);
 // rigid-body wrench report (wrench.hip): the body report of the given families of potentials (an empty list: the zero wrench, unless all[f]: every
 // potential) kept on the device; out [n_families][n_bodies][16], count [n_families][n_bodies]
 int wrench_record(mistark_ctx* ctx, const std::vector<std::vector<int32_t>>& families, const std::vector<char>& all, int v1, int w1, int t0, int q0, int32_t n_bodies,

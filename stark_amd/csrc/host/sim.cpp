@@ -63,6 +63,7 @@ void Stark::ensure_registered()
     bending_recorded = false;
     bending_source = BendingSource{};
     spectrum_recorded = false;
+    linsys_recorded = false;
     wrench_recorded = false;
     wrench_source = WrenchSource{};
     contact_labels = nullptr;
@@ -193,6 +194,11 @@ bool Stark::run_one_step()
     total_evaluations += st.n_evaluations;
 
     if (result == MISTARK_SUCCESSFUL) {
+        if (linsys_recording) {  // first: the matrix as the step's last assembly left it, before any other recording evaluates
+            check(linsys_record(ctx, linsys_op, linsys_m));
+            linsys_time = current_time + dt;
+            linsys_recorded = true;
+        }
         if (force_recording) {
             // the callbacks that precede an evaluation, as the engine's own evaluations have them: at an unchanged state they are answered from the
             // installed tables
@@ -540,6 +546,25 @@ void Stark::get_spectrum_rows(const std::string& name, std::vector<double>& rows
     check(spectrum_fetch_rows(ctx, (int32_t)k, nullptr, &n));
     rows.assign((size_t)10 * n, 0.0);
     if (n > 0) check(spectrum_fetch_rows(ctx, (int32_t)k, rows.data(), nullptr));
+}
+void Stark::record_linsys(bool enabled, int op, int m)
+{
+    if (op != 0 && op != 1) throw std::runtime_error("record_linsys: operator is 0 (A) or 1 (the block-Jacobi preconditioned matrix)");
+    if (m < 1 || m > 256) throw std::runtime_error("record_linsys: m is out of range (1..256)");
+    linsys_recording = enabled;
+    linsys_op = op;
+    linsys_m = m;
+    linsys_recorded = false;
+}
+void Stark::get_linsys(LinsysReport& out)
+{
+    if (!linsys_recording) throw std::runtime_error("get_linsys: linear-system recording is off (record_linsys)");
+    if (!ctx || !linsys_recorded) throw std::runtime_error("get_linsys: no time step has been accepted since recording was switched on");
+    out = LinsysReport{};
+    out.op = linsys_op;
+    out.m = linsys_m;
+    out.time = linsys_time;
+    check(linsys_fetch(ctx, out.record, out.rows));
 }
 void Stark::record_wrench(bool enabled, const Vec3& about)
 {

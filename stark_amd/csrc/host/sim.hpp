@@ -280,6 +280,19 @@ public:
     void get_nodal_spectrum(double* points_out /* n_points x 5 */);
     void get_spectrum_rows(const std::string& name, std::vector<double>& rows /* [n_elem][10] */);
     bool spectrum_recording = false, spectrum_recorded = false;
+    // Linear-system recording (off by default; not in the reference): right after an accepted step, before any other recording, one linear-system report
+    // (include/mistark.h "linear-system report", built-in start vector) of the matrix as the step's last assembly left it: the summary record and the
+    // block rows with the largest share of the lowest and of the highest mode. Refused when the step left no assembled matrix. Off: nothing is launched.
+    struct LinsysReport
+    {
+        double record[16] = {0};
+        double rows[4] = {-1.0, 0.0, -1.0, 0.0};  // low row, its share, high row, its share
+        int op = 1, m = 64;
+        double time = 0.0;
+    };
+    void record_linsys(bool enabled, int op = 1, int m = 64);
+    void get_linsys(LinsysReport& out);
+    bool linsys_recording = false, linsys_recorded = false;
     // Wrench recording (off by default; not in the reference): at the same place, after the before_energy_evaluation callbacks, one body report of the
     // rigid-body wrench report (include/mistark.h "rigid-body wrench report": per family and body a record of 16 doubles and an element count) over
     // seven fixed families of potentials, kept on the device until get_wrench() downloads it. Off: nothing is launched or allocated. A scene without
@@ -329,6 +342,8 @@ private:
     double spectrum_eps = -1.0, spectrum_eps_recorded = 0.0, spectrum_time = 0.0;
     std::vector<int32_t> spectrum_pots;        // the potentials of the report recorded at the last accepted step
     std::vector<std::string> spectrum_names;
+    int linsys_op = 1, linsys_m = 64;
+    double linsys_time = 0.0;
     Vec3 wrench_about = {0.0, 0.0, 0.0};
     double wrench_time = 0.0;
     int32_t wrench_bodies = 0;  // bodies of the report recorded at the last accepted step

@@ -963,6 +963,24 @@ int mistark_sim_get_spectrum_rows(mistark_sim* s, const char* name, int64_t* n_r
     }
     SIM_END
 }
+int mistark_sim_record_linsys(mistark_sim* s, int enabled, int op, int m)
+{
+    SIM_BEGIN
+    s->sim->get_stark().record_linsys(enabled != 0, op, m);
+    SIM_END
+}
+int mistark_sim_get_linsys(mistark_sim* s, int32_t* op, int32_t* m, double* time, double* record, double* rows)
+{
+    SIM_BEGIN
+    Stark::LinsysReport r;
+    s->sim->get_stark().get_linsys(r);
+    if (op) *op = r.op;
+    if (m) *m = r.m;
+    if (time) *time = r.time;
+    if (record) std::copy(r.record, r.record + 16, record);
+    if (rows) std::copy(r.rows, r.rows + 4, rows);
+    SIM_END
+}
 int mistark_sim_record_wrench(mistark_sim* s, int enabled, const double about[3])
 {
     SIM_BEGIN

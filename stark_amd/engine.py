@@ -543,6 +543,53 @@ class Engine:
         self._ck(self.L.mistark_spectrum_potential_report(self.h, ptr, ids.size, int(source), float(eps), out.ctypes.data if out.size else None))
         return out
 
+    # ---- linear-system report (include/mistark.h "linear-system report") -------------------------------------------------------
+    def _linsys_start(self, start):
+        """None: the built-in vector; "rhs": minus the gradient of the last evaluation; otherwise ndofs doubles in DoF order."""
+        if start is None:
+            return None, None
+        if isinstance(start, str):
+            if start != "rhs":
+                raise ValueError("start is None, 'rhs' or an array")
+            v = np.zeros(self.ndofs)
+            self._ck(self.L.mistark_linsys_rhs(self.h, v.ctypes.data))
+        else:
+            v = np.ascontiguousarray(start, dtype=np.float64).reshape(-1)
+            if v.size != self.ndofs:
+                raise ValueError("start has %d entries, the system %d" % (v.size, self.ndofs))
+        return v, v.ctypes.data
+
+    def linsys_report(self, op: int = 1, m: int = 64, start=None) -> "LinsysReport":
+        """Lanczos with full reorthogonalisation on the assembled matrix (op 0: A; 1: the block-Jacobi preconditioned matrix), m steps at the most:
+        the summary record as named fields, ritz [k, 2] (theta ascending, rho) and tri [k, 2] (alpha_j, beta_j)."""
+        v, ptr = self._linsys_start(start)
+        mm = max(int(m), 1)
+        out, ritz, tri, k = np.zeros(16), np.zeros((mm, 2)), np.zeros((mm, 2)), C.c_int32()
+        self._ck(self.L.mistark_linsys_report(self.h, int(op), int(m), ptr, out.ctypes.data, ritz.ctypes.data, tri.ctypes.data, C.byref(k)))
+        return LinsysReport(out, ritz[:k.value].copy(), tri[:k.value].copy())
+
+    def linsys_modes(self, which=(0, -1), op: int = 1, m: int = 64, start=None, x: bool = True, nodal: bool = True) -> dict:
+        """Ritz vectors of the same run: which[i] >= 0 the i-th smallest Ritz value, < 0 counted from the largest. dict(mode [n, 4]: theta, rho, measured
+        residual, index; x [n, ndofs] with x^T D x = 1 (op 1) or |x| = 1 (op 0), DoF order; nodal [n, block rows, 4]: share, |x_r|, trace D_r, smallest
+        squared pivot of D_r)."""
+        v, ptr = self._linsys_start(start)
+        w = np.ascontiguousarray(which, dtype=np.int32).reshape(-1)
+        mode = np.zeros((w.size, 4))
+        xs = np.zeros((w.size, self.ndofs)) if x else None
+        nd = np.zeros((w.size, self.ndofs // 3, 4)) if nodal else None
+        self._ck(self.L.mistark_linsys_modes(self.h, int(op), int(m), ptr, w.ctypes.data if w.size else None, w.size, xs.ctypes.data if x and xs.size else None,
+                                             nd.ctypes.data if nodal and nd.size else None, mode.ctypes.data if mode.size else None))
+        return dict(mode=mode, theta=mode[:, 0], rho=mode[:, 1], residual=mode[:, 2], index=mode[:, 3].astype(np.int64), x=xs, nodal=nd)
+
+    def linsys_potential_shares(self, pots, which: int = 0, op: int = 1, m: int = 64, start=None) -> np.ndarray:
+        """out[len(pots), 4] for one Ritz vector x: sum of q_e = x_e^T H_e x_e over the potential's element Hessians as they stand, sum |q_e|, elements
+        that contribute, first element attaining the largest |q_e| (-1: none). Over all potentials column 0 adds up to theta."""
+        v, ptr = self._linsys_start(start)
+        ids, iptr = self._pot_list(pots)
+        out = np.zeros((ids.size, 4))
+        self._ck(self.L.mistark_linsys_potential_shares(self.h, int(op), int(m), ptr, int(which), iptr, ids.size, out.ctypes.data if out.size else None))
+        return out
+
     def direct_llt(self, rhs):
         """x = A^-1 rhs by the device Cholesky (mistark_direct_llt_rhs); returns (x, success)."""
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)
@@ -660,6 +707,26 @@ def bending_rows_dict(rec, kind):
     return dict(records=rec, kind=int(kind), name=BENDING_KINDS[kind] if 0 <= kind < 2 else None, theta=rec[:, 0], phi=rec[:, 1], rest_angle=rec[:, 2], rate=rec[:, 3],
                 length=rec[:, 4], area=rec[:, 5], kappa=rec[:, 6], kappa_rest=rec[:, 7], moment=rec[:, 8], E_elastic=rec[:, 9], E_damping=rec[:, 10], normal=rec[:, 11:14],
                 group=rec[:, 14].astype(np.int64), flags=flags, degenerate=(flags & 1) != 0, beyond_threshold=(flags & 2) != 0)
+
+
+class LinsysReport:
+    """The summary record of a linear-system report as named fields (record: the 16 doubles), with the Ritz list and the tridiagonal coefficients."""
+    FIELDS = ("k", "flags", "theta_min", "rho_min", "theta_max", "rho_max", "condition", "t_norm", "beta_last", "n_negative", "n_converged", "n_diag_not_pd",
+              "first_diag_not_pd", "min_pivot", "min_pivot_row", "n")
+    INTEGERS = ("k", "flags", "n_negative", "n_converged", "n_diag_not_pd", "first_diag_not_pd", "min_pivot_row", "n")
+
+    def __init__(self, record, ritz=None, tri=None):
+        self.record = np.asarray(record, dtype=np.float64)
+        self.ritz, self.tri = ritz, tri
+        for i, f in enumerate(self.FIELDS):
+            setattr(self, f, int(self.record[i]) if f in self.INTEGERS else float(self.record[i]))
+        self.exhausted = bool(self.flags & 1)
+        self.indefinite = bool(self.flags & 2)
+        self.non_finite = bool(self.flags & 4)
+        self.diag_not_pd = bool(self.flags & 8)
+
+    def __repr__(self):
+        return "LinsysReport(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f in self.FIELDS)
 
 
 def spectrum_rows_dict(rec, nb, spectrum=None):

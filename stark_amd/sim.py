@@ -152,6 +152,8 @@ def _lib():
         L.mistark_sim_get_spectrum.argtypes = [p, I32, I64, D, D, p, p]
         L.mistark_sim_get_nodal_spectrum.argtypes = [p, p]
         L.mistark_sim_get_spectrum_rows.argtypes = [p, C.c_char_p, I64, p, C.c_int64]
+        L.mistark_sim_record_linsys.argtypes = [p, C.c_int, C.c_int, C.c_int]
+        L.mistark_sim_get_linsys.argtypes = [p, I32, I32, D, p, p]
         L.mistark_sim_record_wrench.argtypes = [p, C.c_int, p]
         L.mistark_sim_wrench_sources.argtypes = [p, p, p, p]
         L.mistark_sim_get_wrench.argtypes = [p, I32, I32, I64, D, p, p, p]
@@ -663,6 +665,22 @@ class Simulation:
         if n.value:
             self._ck(self.L.mistark_sim_get_spectrum_rows(self.h, name.encode(), C.byref(n), rec.ctypes.data, n.value))
         return spectrum_rows_dict(rec, 0)
+
+    # ---- linear-system recording ----------------------------------------------------------------------------------------------
+    def record_linsys(self, enabled=True, op=1, m=64):
+        """Every accepted step then keeps the linear-system report of the matrix as the step's last assembly left it (op 0: A; 1: the block-Jacobi
+        preconditioned matrix; at most m Lanczos steps from the built-in start vector)."""
+        self._ck(self.L.mistark_sim_record_linsys(self.h, int(bool(enabled)), int(op), int(m)))
+
+    def linsys(self):
+        """The linear-system report of the last accepted step: dict(time, op, m, report (engine.LinsysReport of the summary record), low_row / low_share and
+        high_row / high_share: the block row with the largest share of the lowest and of the highest mode). Raises while recording is off."""
+        from .engine import LinsysReport
+        op, m, t = C.c_int32(), C.c_int32(), C.c_double()
+        rec, rows = np.zeros(16), np.zeros(4)
+        self._ck(self.L.mistark_sim_get_linsys(self.h, C.byref(op), C.byref(m), C.byref(t), rec.ctypes.data, rows.ctypes.data))
+        return dict(time=t.value, op=op.value, m=m.value, report=LinsysReport(rec), record=rec, low_row=int(rows[0]), low_share=float(rows[1]), high_row=int(rows[2]),
+                    high_share=float(rows[3]))
 
     # ---- wrench recording ------------------------------------------------------------------------------------------------------
     WRENCH_FAMILIES = ("inertia_linear", "inertia_angular", "constraints", "attachments", "contact", "friction", "all")
