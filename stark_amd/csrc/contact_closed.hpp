@@ -16,6 +16,9 @@
 //      point-line and point-point energies have the generic path's bits; the plane distance is (u . n)^2 / |n|^2 instead of (u . n / |n|)^2). Friction: the closed form of the C0 model in the 2-d tangent space.
 // Gradient and Hessian in the local DoF blocks follow by J^T g and J^T H J + S, written block by block in the layout of the generic kernel
 // (k_eval_pgh), which stays as the cross-check (option force_generic; tests compare the two at 1e-11 of the largest entry).
+// Cross-check on synthesised states: tests/test_gpu_contact_synth.py (cases and exact references: tests/contact_cases.py) holds every
+// instantiation to 40-digit derivatives on both friction arms, inside and at the edge of the mollifier, at 1.2 rad per step, close to the
+// surface and beyond dhat, across a 256-lane block.
 #pragma once
 #include "contact_energies.hpp"
 

@@ -199,7 +199,10 @@ __global__ __launch_bounds__(256) void k_eval_custom(PotArgs a, ProgDev p, doubl
         elemH[((size_t)(ba * NB + bb) * a.n_pool + pe) * 9 + ii * 3 + jj] = r.ab;
         elemH[((size_t)(bb * NB + ba) * a.n_pool + pe) * 9 + jj * 3 + ii] = r.ab;
     }
-    if (MODE >= 1 && i == j && on) {
+    if (MODE >= 1 && i == j && a.gpool) {  // node gradients to the pool, summed per block row in list order by k_grad_gather (k_eval_pgh)
+        const int ba = i / 3, ii = i - 3 * ba;
+        a.gpool[((size_t)ba * a.n_gpool + pe) * 3 + ii] = on ? r.a : 0.0;
+    } else if (MODE >= 1 && i == j && on) {
         const int ba = i / 3, ii = i - 3 * ba;
         const int node = a.conn[(size_t)e * a.conn_stride + a.dof_col[ba]];
         if (a.hot_base[ba] >= 0) atomicAdd(&a.grad_hot[((size_t)(blockIdx.x & (HOT_WAYS - 1)) * a.n_hot + a.hot_base[ba] + node) * 3 + ii], r.a);  // (k_eval_pgh)
@@ -584,7 +587,9 @@ std::string emit_source(const CustomProgram& G, const std::vector<int32_t>& in_d
                  "        elemH[((size_t)(ba * NB + bb) * a.n_pool + pe) * 9 + ii * 3 + jj] = r.ab;\n"
                  "        elemH[((size_t)(bb * NB + ba) * a.n_pool + pe) * 9 + jj * 3 + ii] = r.ab;\n    }\n";
         if (MODE >= 1)
-            s += "    if (i == j && on) {\n        const int ba = i / 3, ii = i - 3 * ba;\n"
+            s += "    if (i == j && a.gpool) {\n        const int ba = i / 3, ii = i - 3 * ba;\n"
+                 "        a.gpool[((size_t)ba * a.n_gpool + pe) * 3 + ii] = on ? r.a : 0.0;\n"
+                 "    } else if (i == j && on) {\n        const int ba = i / 3, ii = i - 3 * ba;\n"
                  "        const int node = a.conn[(size_t)e * a.conn_stride + a.dof_col[ba]];\n"
                  "        if (a.hot_base[ba] >= 0) atomicAdd(&a.grad_hot[((size_t)(blockIdx.x & (HOT_WAYS - 1)) * a.n_hot + a.hot_base[ba] + node) * 3 + ii], r.a);\n"
                  "        else atomicAdd(&grad[3 * (size_t)(a.dof_row_off[ba] + node) + ii], r.a);\n    }\n";

@@ -147,14 +147,16 @@ __device__ __forceinline__ void eval_pgh_body(const PotArgs& a, double* __restri
         i++;
     }
     const int j = i + rem;
-    if (!STORE_H && i != j) return;
+    // (STORE_H without a pool: the gradient alone, by the instruction stream that also stores the Hessian — launch_eval, contact tables)
+    const bool store_h = STORE_H && elemH != nullptr;
+    if (!store_h && i != j) return;
     double in[En::Layout::NIN];
     gather_inputs<En>(a, e, in);
     const bool on = element_active<En>(in);
     Loader<HDual> L{in, i, j};
     const HDual r = on ? En::energy(L) : HDual(0.0);
     const int ba = i / 3, ii = i - 3 * ba, bb = j / 3, jj = j - 3 * bb;
-    if (STORE_H) {
+    if (store_h) {
         elemH[((size_t)(ba * NB + bb) * a.n_pool + pe) * 9 + ii * 3 + jj] = r.ab;
         elemH[((size_t)(bb * NB + ba) * a.n_pool + pe) * 9 + jj * 3 + ii] = r.ab;
     }
@@ -865,7 +867,13 @@ static void launch_eval(Context& c, Potential& P, int mode)
             else hipLaunchKernelGGL((k_eval_contact_closed<En, true>), g, b, 0, c.stream, P.args, E, c.elemH.p + P.h_off, c.grad.p);
         }
     } else if (mode == MISTARK_EVAL_P_G) {
-        hipLaunchKernelGGL((k_eval_pgh<En, false>), dim3(grid_for((int64_t)P.args.e_count * NP)), dim3(BLOCK), 0, c.stream, P.args, E, (double*)nullptr, c.grad.p);
+        // Contact and friction tables: the kernel of EVAL_P_G_H without a Hessian pool. k_eval_pgh<En, false> is another instantiation, compiled
+        // without the mixed term, and its gradient differed from EVAL_P_G_H's by up to 7e4 ulp of an entry where a point-line or line-line
+        // distance cancels (tests/test_gpu_contact_synth.py); one instruction stream gives both modes the same bits.
+        if constexpr (has_closed_contact<En>)
+            hipLaunchKernelGGL((k_eval_pgh<En, true>), dim3(grid_for((int64_t)P.args.e_count * NP)), dim3(BLOCK), 0, c.stream, P.args, E, (double*)nullptr, c.grad.p);
+        else
+            hipLaunchKernelGGL((k_eval_pgh<En, false>), dim3(grid_for((int64_t)P.args.e_count * NP)), dim3(BLOCK), 0, c.stream, P.args, E, (double*)nullptr, c.grad.p);
     } else {
         hipLaunchKernelGGL((k_eval_pgh<En, true>), dim3(grid_for((int64_t)P.args.e_count * NP)), dim3(BLOCK), 0, c.stream, P.args, E, c.elemH.p + P.h_off, c.grad.p);
     }
@@ -960,6 +968,7 @@ static void launch_eval_kind(Context& c, Potential& P, int mode)
 {
     if (P.kind == KIND_CUSTOM) {  // no compiled kernel under this name: the caller supplied the expression (custom.hip)
         launch_eval_custom(c, P, mode);
+        if (mode != MISTARK_EVAL_P) launch_grad_gather(c, P);
         return;
     }
     if (mode != MISTARK_EVAL_P && !c.force_generic) {
@@ -2028,7 +2037,9 @@ void prepare(Context& c)
             const bool closed_tri = P.kind != KIND_CUSTOM && !c.force_generic && (P.name == E_TriangleStrain::name || P.name == E_TriangleStrainEO::name);
             // ... and the generic kernels' potentials with several nodes per element (a single node per element: one addition per row, nothing to
             // order); the rows of rigid bodies attached to many points are summed by k_grad_gather_long
-            const bool generic_pool = P.kind != KIND_CUSTOM && P.NB >= 2;
+            // (user-defined potentials too, unless the caller refills them inside the Newton loop: with atomics in arrival order a row that many
+            // elements add to was not reproducible from one evaluation to the next, tests/test_gpu_contact_synth.py)
+            const bool generic_pool = P.NB >= 2 && (P.kind != KIND_CUSTOM || P.part != 1);
             // Tables the CALLER refills inside the Newton loop (a drop-in's contact and friction potentials: part 1, host connectivity): the host-built
             // incidence lists below cost a pass over all block rows and an upload per potential and table change — 1.2 ms per evaluation at 172 k rows,
             // what made the drop-in's energy evaluations 30 times the mirror's. Their node gradients go through the pool of the device-resident
